@@ -10,12 +10,15 @@ the job is data-parallel with the doc embeddings all-gathered (configs[3] at N=8
 i.e. weak scaling at 8192 pairs per rank.
 
     python bench.py [--gpus N --steps K --warmup W]     (N > 1: starts N local ranks itself)
+    python bench.py --full [...]                        (adds rooflines, kernel table, CPU baseline)
+    python bench.py --dump-outputs DIR [...]            (writes the last timed step's outputs)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line. `roofline` is measured live with HIP events around the
-dominant kernel's launches; `cpu_baseline` times the reference's own CPU path (ATen
-nn.GRU / nn.Linear / nn.LayerNorm modules, oracle/aten_ref.py) on a bounded sample on
-this host's cores.
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times the K steps and prints
+the headline (`value`, `ms_per_step`). With --full the timed steps also carry HIP events:
+`roofline` is measured live around the dominant kernel's launches, and `cpu_baseline`
+times the reference's own CPU path (ATen nn.GRU / nn.Linear / nn.LayerNorm modules,
+oracle/aten_ref.py) on a bounded sample on this host's cores.
 """
 from __future__ import annotations
 
@@ -48,15 +51,27 @@ def parse():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: --batch pairs per GPU (configs[3]: 8 x 8192); strong: --batch is the global "
                          "batch, split over the GPUs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: HIP-event kernel timings of the timed "
+                         "steps (rooflines, per-kernel table) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss, query / doc vectors, "
+                         "updated parameters) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-batch", type=int, default=1024, help="pairs per CPU-baseline step (BASELINE.md plan)")
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--cpu-warmup", type=int, default=1)
     ap.add_argument("--cpu-only", action="store_true",
                     help="run only the CPU baseline (e.g. --cpu-batch 8192 --cpu-steps 2: the metric's batch) and "
                          "print its JSON; bench lines attach the committed result (profiles/CPU_B8192)")
-    ap.add_argument("--timing", action="store_true", help="print the per-kernel HIP-event table to stderr")
-    return ap.parse_args()
+    ap.add_argument("--timing", action="store_true",
+                    help="with --full: print the per-kernel HIP-event table to stderr")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.timing and not args.full:
+        ap.error("--timing prints the kernel table of a --full run: add --full")
+    return args
 
 
 def make_batches(n, B, T, V, gen, device):
@@ -71,6 +86,35 @@ def make_batches(n, B, T, V, gen, device):
         d[:, T - pad:] = -1
         out.append((q.to(device), d.to(device)))
     return out
+
+
+DUMP_BUDGET = 60_000_000  # bytes of float32 over all dumped arrays
+
+
+def dump_outputs(dirname, arrays):
+    """Write (name, tensor) pairs as dirname/<name>.npy in float32. If they exceed
+    DUMP_BUDGET together, the small arrays stay whole and every array above a common cap
+    (the largest that fits the budget) keeps `cap` elements: a fixed sample of flat
+    indices (seeded per array, sorted), so two builds run with the same arguments write
+    the same elements."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    sizes = sorted(t.numel() for _, t in arrays)
+    cap, left = None, DUMP_BUDGET // 4
+    for i, n in enumerate(sizes):
+        share = left // (len(sizes) - i)
+        if n > share:
+            cap = share
+            break
+        left -= n
+    for i, (name, t) in enumerate(arrays):
+        t = t.detach()
+        if cap is not None and t.numel() > cap:
+            g = torch.Generator().manual_seed(4321 + i)
+            idx = torch.randperm(t.numel(), generator=g)[:cap].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.float().cpu().numpy())
 
 
 def workload_name(args, world):
@@ -223,6 +267,44 @@ def spawn_local_ranks(n: int) -> int:
     return rc if rc >= 0 else 128 - rc
 
 
+def kernel_figures(kt, args, dt):
+    """The --full fields of the result line from timing.summary() of the timed steps."""
+    # Rooflines from live HIP-event timings. Every region carries its algorithmic FLOPs
+    # and algorithmic HBM bytes; the binding roofline is the one whose floor time
+    # (FLOPs / MFMA peak vs bytes / HBM peak) is larger. `roofline` = dominant kernel
+    # (largest device time per step).
+    peak = BF16_PEAK_TFS if dt == torch.bfloat16 else FP32_PEAK_TFS
+
+    def roof(name):
+        r = kt[name]
+        sec = r["ms_total"] * 1e-3
+        if name == "embed_gather":
+            flop_floor, byte_floor = 0.0, r["bytes"] / (HBM_PEAK_GBS * 1e9)
+        else:
+            flop_floor, byte_floor = r["work"] / (peak * 1e12), r["bytes"] / (HBM_PEAK_GBS * 1e9)
+        if byte_floor >= flop_floor:
+            ach = r["bytes"] / sec / 1e9
+            out = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                   "frac": round(ach / HBM_PEAK_GBS, 4), "bytes_per_launch": round(r["bytes_per_launch"])}
+        else:
+            ach = r["work"] / sec / 1e12
+            out = {"bound": "mfma", "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s",
+                   "frac": round(ach / peak, 4), "flops_per_launch": round(r["work_per_launch"])}
+        out["ms_per_launch"] = round(r["ms_per_launch"], 5)
+        out["launches_per_step"] = r["launches"] // max(args.steps, 1)
+        return out
+
+    dom = max(kt, key=lambda k: kt[k]["ms_total"])
+    roofline = {"kernel": kt[dom]["kernel"], "region": dom, **roof(dom),
+                **pmc_traffic(dom, kt[dom]["kernels"], kt[dom]["launches"] / max(args.steps, 1), args)}
+    extra = {k: roof(k) for k in kt if k != dom}
+    kernels = {k: {"kernel": v["kernel"], "ms_per_step": round(v["ms_total"] / args.steps, 3),
+                   "tflops": round(v["work"] / (v["ms_total"] * 1e-3) / 1e12, 1) if k != "embed_gather" else None,
+                   "gbs": round(v["bytes"] / (v["ms_total"] * 1e-3) / 1e9, 1)}
+               for k, v in sorted(kt.items(), key=lambda kv: -kv[1]["ms_total"])}
+    return {"roofline": roofline, "rooflines_secondary": extra, "kernel_ms_per_step": kernels}
+
+
 def main():
     args = parse()
     if args.cpu_only:
@@ -295,25 +377,24 @@ def main():
         loss.backward()
         tdp.allreduce_grads(params, group)
         opt.step()
-        return loss
+        return loss, qv, dv
 
     for i in range(args.warmup):
-        loss = step(i)
+        loss, qv, dv = step(i)
     first_loss = float(loss.detach()) if args.warmup else float("nan")
     if world > 1:
         tdist.barrier()
     torch.cuda.synchronize()
     timing.reset()
-    timing.enabled = True
+    timing.enabled = args.full  # HIP events around every kernel region of the timed steps
     t0 = time.perf_counter()
     for i in range(args.steps):
-        loss = step(args.warmup + i)
+        loss, qv, dv = step(args.warmup + i)
     torch.cuda.synchronize()
     if world > 1:
         tdist.barrier()
     elapsed = time.perf_counter() - t0
     timing.enabled = False
-    kt = timing.summary()
     final_loss = float(loss.detach())
     # the column-split GRU forward's waits are bounded: a timeout means invalid outputs
     try:
@@ -327,46 +408,20 @@ def main():
     pairs = B * world * args.steps
     value = pairs / elapsed
 
-    # Rooflines from live HIP-event timings. Every region carries its algorithmic FLOPs
-    # and algorithmic HBM bytes; the binding roofline is the one whose floor time
-    # (FLOPs / MFMA peak vs bytes / HBM peak) is larger. `roofline` = dominant kernel
-    # (largest device time per step).
-    peak = BF16_PEAK_TFS if dt == torch.bfloat16 else FP32_PEAK_TFS
-
-    def roof(name):
-        r = kt[name]
-        sec = r["ms_total"] * 1e-3
-        if name == "embed_gather":
-            flop_floor, byte_floor = 0.0, r["bytes"] / (HBM_PEAK_GBS * 1e9)
-        else:
-            flop_floor, byte_floor = r["work"] / (peak * 1e12), r["bytes"] / (HBM_PEAK_GBS * 1e9)
-        if byte_floor >= flop_floor:
-            ach = r["bytes"] / sec / 1e9
-            out = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                   "frac": round(ach / HBM_PEAK_GBS, 4), "bytes_per_launch": round(r["bytes_per_launch"])}
-        else:
-            ach = r["work"] / sec / 1e12
-            out = {"bound": "mfma", "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s",
-                   "frac": round(ach / peak, 4), "flops_per_launch": round(r["work_per_launch"])}
-        out["ms_per_launch"] = round(r["ms_per_launch"], 5)
-        out["launches_per_step"] = r["launches"] // max(args.steps, 1)
-        return out
-
-    dom = max(kt, key=lambda k: kt[k]["ms_total"])
-    roofline = {"kernel": kt[dom]["kernel"], "region": dom, **roof(dom),
-                **pmc_traffic(dom, kt[dom]["kernels"], kt[dom]["launches"] / max(args.steps, 1), args)}
-    extra = {k: roof(k) for k in kt if k != dom}
     step_ms = 1e3 * elapsed / args.steps
-    kernels = {k: {"kernel": v["kernel"], "ms_per_step": round(v["ms_total"] / args.steps, 3),
-                   "tflops": round(v["work"] / (v["ms_total"] * 1e-3) / 1e12, 1) if k != "embed_gather" else None,
-                   "gbs": round(v["bytes"] / (v["ms_total"] * 1e-3) / 1e9, 1)}
-               for k, v in sorted(kt.items(), key=lambda kv: -kv[1]["ms_total"])}
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed step holds after its last call: the loss, both towers'
+        # vectors and the parameters Adam has just updated
+        dump_outputs(args.dump_outputs, [("loss", loss), ("query_vectors", qv), ("doc_vectors", dv)]
+                     + [("param." + n, p) for n, p in model.named_parameters()])
+    # everything below the headline is measured only with --full
+    figures = kernel_figures(timing.summary(), args, dt) if args.full else {}
     if args.timing and rank == 0:
         import sys
-        print(json.dumps(kernels, indent=1), file=sys.stderr)
+        print(json.dumps(figures["kernel_ms_per_step"], indent=1), file=sys.stderr)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
         if os.path.exists(CPU_B8192):  # the metric's batch, measured separately (minutes of CPU time)
             with open(CPU_B8192) as f:
@@ -383,12 +438,11 @@ def main():
                        "parallelism": f"dp{world}", "loss": args.loss,
                        "collectives": (("rccl" if backend == "nccl" else backend) + (" (forced at one rank)" if forced else ""))
                        if tdist.is_initialized() else None},
-            "roofline": roofline,
-            "rooflines_secondary": extra,
-            "kernel_ms_per_step": kernels,
+            **figures,
             "loss_first_last": [round(first_loss, 5), round(final_loss, 5)],
-            "cpu_baseline": cpu,
         }
+        if args.full:
+            line["cpu_baseline"] = cpu
         print(json.dumps(line), file=out, flush=True)
     if tdist.is_initialized():
         tdist.destroy_process_group()

@@ -175,6 +175,34 @@ long tt_gru_fwd_ws_size(int dtype, int nrec, int B, int T, int H, long ldg, long
  * kernel); needs the device. */
 int tt_gru_fwd_launches_for(int dtype, int nrec, int B, int T, int H, long ldg, long ldy);
 
+/* Inference forward of the same layer (no gradient will be taken): the recurrence of
+ * tt_gru_fwd with drop_p = 0, without the saved pre-activations and the dropout copy, and
+ * with the layer output optional. Every value it writes is bit-identical to what tt_gru_fwd
+ * (drop_p = 0) writes at the same position: same kernels' product order and gate cell.
+ *   y      given: the layer output, as tt_gru_fwd's y.
+ *   hfinal given: h after the recurrence's last step (t = T-1 for dir 0, t = 0 for dir 1) of
+ *          batch row b at hfinal[b*ldf + j], j < H, in dtype. The two directions of a tower
+ *          may point at columns 0 and H of one [B, 2H] buffer (ldf = 2H).
+ * Both may be given; at least one must be, and all records of a call must agree on which are
+ * NULL (else TT_EINVAL). Alignment as tt_gru_fwd, plus (ldf * element size) % 16 == 0.
+ * ws / ws_bytes follow tt_gru_fwd's contract (column-split kernel, status word at ws[0..3]);
+ * tt_gru_fwd_ws_size and tt_gru_fwd_launches_for answer for this call as well (same launch
+ * geometry). scratch: tt_gru_infer_scratch_size bytes per recurrence, 16-byte aligned; only
+ * the per-step kernel uses it (the fp32 state, and without y the image of h_{s-1} its
+ * product reads), so it is 0 / may be NULL wherever a persistent kernel applies. */
+typedef struct {
+  const void* g; const void* whh; const float* bhn; /* as tt_gru_fwd_rec                  */
+  void* y;        /* [B*T, ldy] layer output, or NULL (final-only)                         */
+  void* hfinal;   /* [B, ldf] dtype: h after the last step, or NULL                        */
+  void* scratch;  /* tt_gru_infer_scratch_size bytes per recurrence (may be 0)             */
+  int dir;
+} tt_gru_infer_rec;
+int  tt_gru_fwd_infer(int dtype, const tt_gru_infer_rec* recs, int nrec, int B, int T, int H, long ldg,
+                      long ldy, long ldf, void* ws, long ws_bytes, void* stream);
+/* Bytes of tt_gru_infer_rec.scratch for one recurrence of this call shape under the current
+ * options (final_only: y is NULL); 0 where the state stays on chip. */
+long tt_gru_infer_scratch_size(int dtype, int B, int T, int H, int final_only);
+
 /* Backward (BPTT) of tt_gru_fwd. Produces dL/dg (= dgx, feeds dWih, dbih and the
  * layer-input gradient) and dL/dgh (feeds dWhh), plus bias partial sums (one row per
  * 128-row batch tile: tt_gru_bias_rows(B) rows; columns r|z|n|ghn; reduce with tt_colsum:

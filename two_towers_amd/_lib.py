@@ -64,6 +64,13 @@ class GruFwdRec(ctypes.Structure):
     ]
 
 
+class GruInferRec(ctypes.Structure):  # include/tt_hip.h tt_gru_infer_rec
+    _fields_ = [
+        ("g", c_void_p), ("whh", c_void_p), ("bhn", c_void_p), ("y", c_void_p), ("hfinal", c_void_p),
+        ("scratch", c_void_p), ("dir", c_int),
+    ]
+
+
 class GruBwdRec(ctypes.Structure):
     _fields_ = [
         ("save", c_void_p), ("y", c_void_p), ("dy", c_void_p), ("dfinal", c_void_p), ("whh", c_void_p),
@@ -130,6 +137,9 @@ _SIGS = {
     "tt_gru_fwd_launches": (c_int, [c_int, c_int, c_int]),
     "tt_gru_fwd_ws_size": (c_long, [c_int, c_int, c_int, c_int, c_int, c_long, c_long]),
     "tt_gru_fwd_launches_for": (c_int, [c_int, c_int, c_int, c_int, c_int, c_long, c_long]),
+    "tt_gru_fwd_infer": (c_int, [c_int, POINTER(GruInferRec), c_int, c_int, c_int, c_int, c_long, c_long, c_long,
+                                 c_void_p, c_long, c_void_p]),
+    "tt_gru_infer_scratch_size": (c_long, [c_int, c_int, c_int, c_int, c_int]),
     "tt_proj_head_fwd": (c_int, [c_int, POINTER(HeadFwdIO), c_int, c_int, c_int, c_float, c_void_p]),
     "tt_proj_head_bwd": (c_int, [c_int, POINTER(HeadBwdIO), c_int, c_int, c_int, c_float, c_void_p]),
     "tt_proj_head_bwd_ws_size": (c_long, [c_int, c_int, c_int]),

@@ -35,6 +35,19 @@ struct FwdArgs {
   int dbg;  // diagnostic build only: 1 no stores, 2 no G loads
 #endif
 };
+// Arguments of the inference kernels (tt_gru_fwd_infer): per recurrence the [B, ldf]
+// final-state output (or null) and the per-step kernel's two-slot image [2][B][H] of h in
+// the compute dtype. x1 and save of the records are unused.
+struct InfArgs : FwdArgs {
+  void* hfin[4];
+  void* himg[4];
+  long ldf;
+};
+// what the shared kernel bodies read of them outside `if constexpr (INF)`
+TT_DEV void* inf_hfin(const FwdArgs&, int) { return nullptr; }
+TT_DEV void* inf_hfin(const InfArgs& a, int rz) { return a.hfin[rz]; }
+TT_DEV long inf_ldf(const FwdArgs&) { return 0; }
+TT_DEV long inf_ldf(const InfArgs& a) { return a.ldf; }
 
 struct BwdRec {
   const void* save; const void* y; const void* dy; const float* dfinal; const void* whh;
@@ -88,8 +101,13 @@ struct GateRows {
 // half the W_hh traffic per FLOP and twice the MFMA work per K-tile barrier): at configs[4]
 // (H 1024, B 8192) 48.0-48.6 vs 50.3-51.5 ms per layer. A 4-stage LDS ring with counted
 // waits on 128-row tiles (one workgroup per CU) measured 85.7 ms.
-template <typename T, int BMR, int NS = 2>  // NS: LDS stages of the product (DLoop)
-__global__ __launch_bounds__(2 * BMR) void gru_fwd_step(FwdArgs a) {
+// INF: the inference form (tt_gru_fwd_infer). No saved pre-activations and no dropout copy;
+// Y is optional (final-only: h_{s-1} for the product then comes from a two-slot image in the
+// compute dtype, row stride H, beside the fp32 state), and the last step's h goes to hfin.
+// Same product and cell: what it writes is bit-identical to the training form's Y.
+template <typename T, int BMR, int NS = 2, typename A = FwdArgs>  // NS: LDS stages of the product (DLoop)
+__global__ __launch_bounds__(2 * BMR) void gru_fwd_step(A a) {
+  constexpr bool INF = std::is_same_v<A, InfArgs>;  // the inference form (tt_gru_fwd_infer)
   constexpr int NT = 2 * BMR;
   using ML = ttg::DLoop<T, false, false, BMR, 192, BMR / 64, 2, NS>;
   __shared__ __attribute__((aligned(16))) char lds[ML::LDS_BYTES];
@@ -122,6 +140,9 @@ __global__ __launch_bounds__(2 * BMR) void gru_fwd_step(FwdArgs a) {
   const float* hs_prv = R.hs + (long)prv * a.B * H;
   if (prod) {
     ttg::KCPlain<T> la{Y + (long)tp * a.ldy, (long)T_ * a.ldy, m0, a.B};
+    if constexpr (INF) {
+      if (!Y) la = ttg::KCPlain<T>{static_cast<const T*>(a.himg[rz]) + (long)prv * a.B * H, (long)H, m0, a.B};
+    }
     GateRows<T> lb{static_cast<const T*>(R.whh), H, j0};
     const int nk = (H * (int)sizeof(T) + ttg::KTB - 1) / ttg::KTB;
     ML::run(la, lb, H, 0, nk, lds, acc);
@@ -181,6 +202,13 @@ __global__ __launch_bounds__(2 * BMR) void gru_fwd_step(FwdArgs a) {
           // in fp32, so 1-z and 1-n^2 keep full precision even with bf16 storage
           gru_cell(xr[e], xz[e], xn[e], Lr[e], Lz[e], Ln[e], bn[e], hp[e], y[e], sr[e], sz[e], sn[e], sg[e]);
         st8(hs_cur + (long)b * H + j, y);
+        if constexpr (INF) {
+          if (Yw) st8(Yw + row * a.ldy + j, y);
+          else st8(static_cast<T*>(a.himg[rz]) + ((long)cur * a.B + b) * H + j, y);
+          T* hf = static_cast<T*>(a.hfin[rz]);
+          if (hf && s == T_ - 1) st8(hf + (long)b * a.ldf + j, y);
+          continue;
+        }
         st8(Yw + row * a.ldy + j, y);
         // saved pre-activations and the dropout copy are only read by later kernels:
         // stream them past L2 (sc1) so Whh and the h_{s-1} rows stay resident
@@ -1144,8 +1172,13 @@ TT_DEV void fwd_kstep(const bf16_t* W, int H, int Q, int q, int kt, bool mm, con
 // vmcnt bookkeeping at its first K-tiles counts the previous block's epilogue stores and
 // the gate loads exactly instead of the loop-merged minimum: with one in-order counter
 // that minimum made the first W_hh waits of every block also wait for those stores.
-template <int D, int NKT>
-__global__ __launch_bounds__(PNT) void gru_fwd_seq(FwdArgs a) {
+// INF: the inference form (tt_gru_fwd_infer). The epilogue keeps its six stores, so the
+// counted waits hold as they are, but the four of the saved pre-activations go through a
+// resource of num_records 0 (dropped: no traffic), Y's too when only the final state is
+// wanted, and the dropout copy's slot carries the last step's h to hfin [B, ldf].
+template <int D, int NKT, typename A = FwdArgs>
+__global__ __launch_bounds__(PNT) void gru_fwd_seq(A a) {
+  constexpr bool INF = std::is_same_v<A, InfArgs>;  // the inference form (tt_gru_fwd_infer)
   __shared__ __attribute__((aligned(16))) char lds[P_LDS];
   char* hb = lds;
   char* bst = lds + P_HB;
@@ -1174,9 +1207,12 @@ __global__ __launch_bounds__(PNT) void gru_fwd_seq(FwdArgs a) {
   // every wave issues the same count and the waits above stay exact
   const long r0w = (long)m0 * T_;
   const __amdgpu_buffer_rsrc_t rG = tt_rsrc_n(G + r0w * a.ldg, true);
-  const __amdgpu_buffer_rsrc_t rY = tt_rsrc_n(Yw + r0w * a.ldy, true);
-  const __amdgpu_buffer_rsrc_t rX1 = tt_rsrc_n(X1 ? X1 + r0w * a.ldy : Yw, X1 != nullptr);
-  const __amdgpu_buffer_rsrc_t rS = tt_rsrc_n(S + r0w * 4L * H, true);
+  bf16_t* HF = static_cast<bf16_t*>(inf_hfin(a, rz));
+  const __amdgpu_buffer_rsrc_t rY =
+      INF ? tt_rsrc_n(Yw ? (const void*)(Yw + r0w * a.ldy) : G, Yw != nullptr) : tt_rsrc_n(Yw + r0w * a.ldy, true);
+  const __amdgpu_buffer_rsrc_t rX1 = INF ? tt_rsrc_n(HF ? (const void*)(HF + (long)m0 * inf_ldf(a)) : G, HF != nullptr)
+                                         : tt_rsrc_n(X1 ? X1 + r0w * a.ldy : Yw, X1 != nullptr);
+  const __amdgpu_buffer_rsrc_t rS = INF ? tt_rsrc_n(G, false) : tt_rsrc_n(S + r0w * 4L * H, true);
 #ifdef TT_DIAG
   const bool gok = rowok && !(a.dbg & 2), sok = rowok && !(a.dbg & 1);
 #else
@@ -1300,17 +1336,27 @@ __global__ __launch_bounds__(PNT) void gru_fwd_seq(FwdArgs a) {
         const uint32_t oy = sok ? (uint32_t)(lrow * (int)a.ldy + j) * 2u : 0x80000000u;
         const uint32_t os = sok ? (uint32_t)(lrow * 4 * H + j) * 2u : 0x80000000u;
         st16_buf(rY, oy, 0, pack8bf(y));
-        st16_buf(rS, os, 0, pack8bf(sr));
-        st16_buf(rS, os, 2 * H, pack8bf(sz));
-        st16_buf(rS, os, 4 * H, pack8bf(sn));
-        st16_buf(rS, os, 6 * H, pack8bf(sg));
-        if (X1 && a.drop_thresh) {
+        if constexpr (INF) {
+          // same six stores; rS drops its four, the sixth is the final state's (last step only)
+          const uint32_t of = sok && s == T_ - 1 ? (uint32_t)(rl * (int)a.ldf + j) * 2u : 0x80000000u;
+          st16_buf(rS, os, 0, pack8bf(y));
+          st16_buf(rS, os, 2 * H, pack8bf(y));
+          st16_buf(rS, os, 4 * H, pack8bf(y));
+          st16_buf(rS, os, 6 * H, pack8bf(y));
+          st16_buf(rX1, of, 0, pack8bf(y));
+        } else {
+          st16_buf(rS, os, 0, pack8bf(sr));
+          st16_buf(rS, os, 2 * H, pack8bf(sz));
+          st16_buf(rS, os, 4 * H, pack8bf(sn));
+          st16_buf(rS, os, 6 * H, pack8bf(sg));
+          if (X1 && a.drop_thresh) {
 #pragma unroll
-          for (int e = 0; e < 8; ++e)
-            y[e] *= tt_dropout_scale(R.seed, R.row0 + (uint32_t)row, (uint32_t)(R.col0 + j + e), a.drop_thresh,
-                                     a.inv_keep);
+            for (int e = 0; e < 8; ++e)
+              y[e] *= tt_dropout_scale(R.seed, R.row0 + (uint32_t)row, (uint32_t)(R.col0 + j + e), a.drop_thresh,
+                                       a.inv_keep);
+          }
+          st16_buf(rX1, oy, 0, pack8bf(y));
         }
-        st16_buf(rX1, oy, 0, pack8bf(y));
       }
       TT_STAMP(e2);
       TT_ACC(4, e2 - e1);  // gate math + stores issued
@@ -1543,8 +1589,14 @@ TT_DEV void xc_stage(float* stg, const f32x4 (&acc)[2][3]) {
 // the members publish each half step (chunks 0-3, 4-7) on its own counter, so a member
 // waits for the first half of step s only while it computes the second half of step s-1
 // of its own. Same arithmetic, same order, same outputs as gru_fwd_xc (bit-identical).
-template <int H, bool DROP>
-__global__ __launch_bounds__(xc::NT, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) void gru_fwd_xcp(FwdArgs a, XcWs ws) {
+// INF: the inference form (tt_gru_fwd_infer), as in gru_fwd_seq: still exactly six output
+// stores after the exchange store (the publish waits count them), the saved pre-activations'
+// four through a resource of num_records 0, Y's too when it is not wanted, and the dropout
+// copy's slot carries h to hfin through a resource that is live at a round's last step only.
+template <int H, bool DROP, typename A = FwdArgs>
+__global__ __launch_bounds__(xc::NT, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) void gru_fwd_xcp(A a, XcWs ws) {
+  constexpr bool INF = std::is_same_v<A, InfArgs>;  // the inference form (tt_gru_fwd_infer)
+  static_assert(!(INF && DROP), "no dropout copy in the inference form");
   using C = xc::Cfg<H>;
   constexpr int M = C::M, NKT = C::NKT;
   __shared__ __attribute__((aligned(16))) char lds[C::LDS];
@@ -1670,9 +1722,13 @@ __global__ __launch_bounds__(xc::NT, 1) __attribute__((amdgpu_waves_per_eu(1, 1)
     const __amdgpu_buffer_rsrc_t rGn = g_rsrc(nxt);
     const long r0w = (long)(cur.nrow > 0 ? cur.rb0 : 0) * T_;
     const bool on = cur.nrow > 0;
-    const __amdgpu_buffer_rsrc_t rY = tt_rsrc_n(Yw + r0w * a.ldy, on);
-    const __amdgpu_buffer_rsrc_t rX1 = tt_rsrc_n(X1 ? X1 + r0w * a.ldy : Yw, on && X1 != nullptr);
-    const __amdgpu_buffer_rsrc_t rS = tt_rsrc_n(S + r0w * 4L * H, on);
+    bf16_t* HF = static_cast<bf16_t*>(inf_hfin(a, rz));
+    const __amdgpu_buffer_rsrc_t rY =
+        INF ? tt_rsrc_n(Yw ? (const void*)(Yw + r0w * a.ldy) : G, on && Yw != nullptr) : tt_rsrc_n(Yw + r0w * a.ldy, on);
+    const __amdgpu_buffer_rsrc_t rX1 =
+        INF ? tt_rsrc_n(HF ? (const void*)(HF + (long)(on ? cur.rb0 : 0) * inf_ldf(a)) : G, on && HF != nullptr && cur.s == T_ - 1)
+            : tt_rsrc_n(X1 ? X1 + r0w * a.ldy : Yw, on && X1 != nullptr);
+    const __amdgpu_buffer_rsrc_t rS = INF ? tt_rsrc_n(G, false) : tt_rsrc_n(S + r0w * 4L * H, on);
     const __amdgpu_buffer_rsrc_t rdst_h = rx[idx & 1];
     const int t = cur.t;
 #pragma unroll
@@ -1756,16 +1812,24 @@ __global__ __launch_bounds__(xc::NT, 1) __attribute__((amdgpu_waves_per_eu(1, 1)
         // outputs: read only by later kernels (cache policy XC_OUT_AUX; offsets folded into
         // the lane offset, soffset 0, as st16_buf does)
         st16_buf_aux<XC_OUT_AUX>(rY, (int)oy, yb);
-        st16_buf_aux<XC_OUT_AUX>(rS, (int)os, pack8bf(sr));
-        st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 2u * H), pack8bf(sz));
-        st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 4u * H), pack8bf(sn));
-        st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 6u * H), pack8bf(sg));
-        if constexpr (DROP) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) y[e] *= msk[e];
-          st16_buf_aux<XC_OUT_AUX>(rX1, (int)oy, pack8bf(y));
+        if constexpr (INF) {
+          st16_buf_aux<XC_OUT_AUX>(rS, (int)os, yb);
+          st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 2u * H), yb);
+          st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 4u * H), yb);
+          st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 6u * H), yb);
+          st16_buf_aux<XC_OUT_AUX>(rX1, (int)(ok ? (uint32_t)(rr * (int)a.ldf + j) * 2u : xc::OOB), yb);
         } else {
-          st16_buf_aux<XC_OUT_AUX>(rX1, (int)oy, yb);
+          st16_buf_aux<XC_OUT_AUX>(rS, (int)os, pack8bf(sr));
+          st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 2u * H), pack8bf(sz));
+          st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 4u * H), pack8bf(sn));
+          st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 6u * H), pack8bf(sg));
+          if constexpr (DROP) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) y[e] *= msk[e];
+            st16_buf_aux<XC_OUT_AUX>(rX1, (int)oy, pack8bf(y));
+          } else {
+            st16_buf_aux<XC_OUT_AUX>(rX1, (int)oy, yb);
+          }
         }
       }
       // end of a half step: every wave's exchange stores done (only the six output stores
@@ -1834,8 +1898,11 @@ struct Cfg {
 static_assert(Cfg<512>::LDS <= 163840, "gru_fwd_xs LDS budget");
 }  // namespace xs
 
-template <int H, bool DROP>
-__global__ __launch_bounds__(xs::NT, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) void gru_fwd_xs(FwdArgs a, XcWs ws) {
+// INF: the inference form, exactly as in gru_fwd_xcp (six stores, dropped where unwanted).
+template <int H, bool DROP, typename A = FwdArgs>
+__global__ __launch_bounds__(xs::NT, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) void gru_fwd_xs(A a, XcWs ws) {
+  constexpr bool INF = std::is_same_v<A, InfArgs>;  // the inference form (tt_gru_fwd_infer)
+  static_assert(!(INF && DROP), "no dropout copy in the inference form");
   using C = xc::Cfg<H>;
   constexpr int M = C::M, NKT = C::NKT, QPW = C::QPW;
 #ifdef TT_DIAG  // timing only (results wrong): 1 no output stores, 2 no G loads, 4 no exchange
@@ -2021,9 +2088,13 @@ __global__ __launch_bounds__(xs::NT, 1) __attribute__((amdgpu_waves_per_eu(2, 2)
     const __amdgpu_buffer_rsrc_t rGn = g_rsrc(nxt);
     const long r0w = (long)(cur.nrow > 0 ? cur.rb0 : 0) * T_;
     const bool on = cur.nrow > 0;
-    const __amdgpu_buffer_rsrc_t rY = tt_rsrc_n(Yw + r0w * a.ldy, on);
-    const __amdgpu_buffer_rsrc_t rX1 = tt_rsrc_n(X1 ? X1 + r0w * a.ldy : Yw, on && X1 != nullptr);
-    const __amdgpu_buffer_rsrc_t rS = tt_rsrc_n(S + r0w * 4L * H, on);
+    bf16_t* HF = static_cast<bf16_t*>(inf_hfin(a, rz));
+    const __amdgpu_buffer_rsrc_t rY =
+        INF ? tt_rsrc_n(Yw ? (const void*)(Yw + r0w * a.ldy) : G, on && Yw != nullptr) : tt_rsrc_n(Yw + r0w * a.ldy, on);
+    const __amdgpu_buffer_rsrc_t rX1 =
+        INF ? tt_rsrc_n(HF ? (const void*)(HF + (long)(on ? cur.rb0 : 0) * inf_ldf(a)) : G, on && HF != nullptr && cur.s == T_ - 1)
+            : tt_rsrc_n(X1 ? X1 + r0w * a.ldy : Yw, on && X1 != nullptr);
+    const __amdgpu_buffer_rsrc_t rS = INF ? tt_rsrc_n(G, false) : tt_rsrc_n(S + r0w * 4L * H, on);
     const __amdgpu_buffer_rsrc_t rdst_h = rx[idx & 1];
     const int t = cur.t;
     const bool first = cur.s == 0;
@@ -2070,17 +2141,25 @@ __global__ __launch_bounds__(xs::NT, 1) __attribute__((amdgpu_waves_per_eu(2, 2)
         const uint32_t oy = okd ? (uint32_t)(lrow * (int)a.ldy + j) * 2u : xc::OOB;
         const uint32_t os = okd ? (uint32_t)(lrow * 4 * H + j) * 2u : xc::OOB;
         st16_buf_aux<XC_OUT_AUX>(rY, (int)oy, yb);
-        st16_buf_aux<XC_OUT_AUX>(rS, (int)os, pack8bf(sr));
-        st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 2u * H), pack8bf(sz));
-        st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 4u * H), pack8bf(sn));
-        st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 6u * H), pack8bf(sg));
-        if constexpr (DROP) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e)
-            y[e] *= tt_dropout_scale(R.seed, R.row0 + grow, (uint32_t)(R.col0 + j + e), a.drop_thresh, a.inv_keep);
-          st16_buf_aux<XC_OUT_AUX>(rX1, (int)oy, pack8bf(y));
+        if constexpr (INF) {
+          st16_buf_aux<XC_OUT_AUX>(rS, (int)os, yb);
+          st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 2u * H), yb);
+          st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 4u * H), yb);
+          st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 6u * H), yb);
+          st16_buf_aux<XC_OUT_AUX>(rX1, (int)(okd ? (uint32_t)(rr * (int)a.ldf + j) * 2u : xc::OOB), yb);
         } else {
-          st16_buf_aux<XC_OUT_AUX>(rX1, (int)oy, yb);
+          st16_buf_aux<XC_OUT_AUX>(rS, (int)os, pack8bf(sr));
+          st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 2u * H), pack8bf(sz));
+          st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 4u * H), pack8bf(sn));
+          st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 6u * H), pack8bf(sg));
+          if constexpr (DROP) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+              y[e] *= tt_dropout_scale(R.seed, R.row0 + grow, (uint32_t)(R.col0 + j + e), a.drop_thresh, a.inv_keep);
+            st16_buf_aux<XC_OUT_AUX>(rX1, (int)oy, pack8bf(y));
+          } else {
+            st16_buf_aux<XC_OUT_AUX>(rX1, (int)oy, yb);
+          }
         }
       }
       if (c == 3 || c == 7) asm volatile("s_nop 0\n\ts_waitcnt vmcnt(6)" ::: "memory");  // s_nop 0: marker (test_host)
@@ -2105,7 +2184,6 @@ __global__ __launch_bounds__(xs::NT, 1) __attribute__((amdgpu_waves_per_eu(2, 2)
     rGc = rGn;
   }
 }
-
 #ifdef TT_DIAG
 }  // namespace
 extern "C" int tt_diag_fwd_prof(unsigned long long* out) {  // [2048][8] host buffer
@@ -2206,6 +2284,8 @@ struct XcDev {
   int cus = 0;
   int occ[2][2] = {{0, 0}, {0, 0}};  // [H 256 / 512][DROP]
   int occ_xs[2] = {0, 0};            // gru_fwd_xs<512, DROP>
+  int occ_inf[2] = {0, 0};           // gru_fwd_xcp<256 / 512, false, InfArgs>
+  int occ_xs_inf = 0;                // gru_fwd_xs<512, false, InfArgs>
 };
 static std::mutex g_xc_mu;
 static XcDev g_xc[64];
@@ -2218,6 +2298,11 @@ template <bool DROP>
 static const void* xs_kernel() {
   return reinterpret_cast<const void*>(&gru_fwd_xs<512, DROP>);
 }
+template <int H>
+static const void* xc_infer_kernel() {
+  return reinterpret_cast<const void*>(&gru_fwd_xcp<H, false, InfArgs>);
+}
+static const void* xs_infer_kernel() { return reinterpret_cast<const void*>(&gru_fwd_xs<512, false, InfArgs>); }
 // the specialized-wave form (gru_fwd_xs) where it is selected and built (H 512)
 static bool xs_on(int H) { return H == 512 && tt::opt(tt::OPT_GRU_FWD_XS) != 0; }
 
@@ -2236,6 +2321,9 @@ static int xc_device(XcDev** out) {
       for (int d = 0; d < 2; ++d) TT_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&x.occ[h][d], k[h][d], xc::NT, 0));
     const void* kx[2] = {xs_kernel<false>(), xs_kernel<true>()};
     for (int d = 0; d < 2; ++d) TT_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&x.occ_xs[d], kx[d], xs::NT, 0));
+    const void* ki[2] = {xc_infer_kernel<256>(), xc_infer_kernel<512>()};
+    for (int h = 0; h < 2; ++h) TT_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&x.occ_inf[h], ki[h], xc::NT, 0));
+    TT_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&x.occ_xs_inf, xs_infer_kernel(), xs::NT, 0));
     x.cus = cus;
   }
   *out = &x;
@@ -2244,7 +2332,7 @@ static int xc_device(XcDev** out) {
 
 // Launch geometry of the column-split forward, or false where it does not apply.
 static bool xc_geometry(const XcDev& dev, int dtype, int H, int nrec, int B, int T, long ldg, long ldy, bool drop,
-                        XcGeo& g) {
+                        XcGeo& g, bool inf = false) {
   const int v = tt::opt(tt::OPT_GRU_FWD_XC);
   if (v == 0 || dtype != TT_DT_BF16 || (H != 512 && H != 256) || tt::opt(tt::OPT_GRU_STEP) == 1) return false;
   const int M = H / 64;
@@ -2252,7 +2340,8 @@ static bool xc_geometry(const XcDev& dev, int dtype, int H, int nrec, int B, int
   const int ng = 8 * qg;
   if (qg < 1 || ng > XC_MAX_GROUPS || ng % nrec != 0) return false;
   // every member must be resident at once: one workgroup per CU, grid <= CUs
-  const int occ = xs_on(H) ? dev.occ_xs[drop] : dev.occ[H == 512][drop];
+  const int occ = inf ? (xs_on(H) ? dev.occ_xs_inf : dev.occ_inf[H == 512])
+                      : (xs_on(H) ? dev.occ_xs[drop] : dev.occ[H == 512][drop]);
   if (occ < 1 || ng * M > dev.cus * occ) return false;
   const int gpr = ng / nrec;
   // auto mode: only where every group gets at least half a round of rows
@@ -2277,14 +2366,15 @@ static bool xc_geometry(const XcDev& dev, int dtype, int H, int nrec, int B, int
   return true;
 }
 
-static int xc_plan(int dtype, int nrec, int B, int T, int H, long ldg, long ldy, bool drop, XcGeo& g, bool* ok) {
+static int xc_plan(int dtype, int nrec, int B, int T, int H, long ldg, long ldy, bool drop, XcGeo& g, bool* ok,
+                   bool inf = false) {
   *ok = false;
   if (dtype != TT_DT_BF16 || nrec < 1 || nrec > 4 || B <= 0 || T <= 0 || (H != 256 && H != 512) ||
       tt::opt(tt::OPT_GRU_FWD_XC) == 0)
     return 0;
   XcDev* x = nullptr;
   TT_PROPAGATE(xc_device(&x));
-  *ok = xc_geometry(*x, dtype, H, nrec, B, T, ldg, ldy, drop, g);
+  *ok = xc_geometry(*x, dtype, H, nrec, B, T, ldg, ldy, drop, g, inf);
   return 0;
 }
 
@@ -2299,14 +2389,16 @@ extern "C" long tt_gru_fwd_ws_size(int dtype, int nrec, int B, int T, int H, lon
 
 // Launches the column-split forward when it applies and ws is large enough (*used = true);
 // a grid the runtime will not make co-resident leaves *used false (row-owning fallback).
-static int gru_fwd_xc_launch(const FwdArgs& a, int nrec, int B, int T, int H, long ldg, long ldy, void* ws,
+template <typename A>  // FwdArgs: the training kernels; InfArgs: the inference kernels
+static int gru_fwd_xc_launch(const A& a, int nrec, int B, int T, int H, long ldg, long ldy, void* ws,
                              long ws_bytes, hipStream_t st, bool* used) {
+  constexpr bool inf = std::is_same_v<A, InfArgs>;
   *used = false;
   if (!ws) return 0;
-  const bool drop = a.drop_thresh != 0 && a.r[0].x1 != nullptr;
+  const bool drop = !inf && a.drop_thresh != 0 && a.r[0].x1 != nullptr;
   XcGeo g;
   bool ok = false;
-  TT_PROPAGATE(xc_plan(TT_DT_BF16, nrec, B, T, H, ldg, ldy, drop, g, &ok));
+  TT_PROPAGATE(xc_plan(TT_DT_BF16, nrec, B, T, H, ldg, ldy, drop, g, &ok, inf));
   if (!ok || ws_bytes < g.bytes) return 0;
   TT_CHECK_ARG(((uintptr_t)ws & 255) == 0, "tt_gru_fwd: ws must be 256-byte aligned");
   char* base = static_cast<char*>(ws);
@@ -2315,13 +2407,14 @@ static int gru_fwd_xc_launch(const FwdArgs& a, int nrec, int B, int T, int H, lo
   g.w.err = g.w.cnt + g.ng * xc::CSTR;
   g.w.xb = reinterpret_cast<bf16_t*>(base + g.img_off);
   TT_CHECK_HIP(hipMemsetAsync(base + XC_HDR, 0, g.cnt_bytes, st));
-  FwdArgs ak = a;
+  A ak = a;
   XcWs wk = g.w;
   void* args[] = {&ak, &wk};
   const bool xs = xs_on(H);
-  const void* fn = xs ? (drop ? xs_kernel<true>() : xs_kernel<false>())
-                 : H == 512 ? (drop ? xc_kernel<512, true>() : xc_kernel<512, false>())
-                            : (drop ? xc_kernel<256, true>() : xc_kernel<256, false>());
+  const void* fn = inf ? (xs ? xs_infer_kernel() : H == 512 ? xc_infer_kernel<512>() : xc_infer_kernel<256>())
+                   : xs ? (drop ? xs_kernel<true>() : xs_kernel<false>())
+                   : H == 512 ? (drop ? xc_kernel<512, true>() : xc_kernel<512, false>())
+                              : (drop ? xc_kernel<256, true>() : xc_kernel<256, false>());
   const int nt = xs ? xs::NT : xc::NT;
   // A plain launch by default: xc_plan has already checked the grid (<= one workgroup per
   // CU) against the occupancy query, which is all a cooperative launch checks on gfx950
@@ -2348,6 +2441,65 @@ extern "C" int tt_gru_fwd_launches_for(int dtype, int nrec, int B, int T, int H,
   bool ok = false;
   if (xc_plan(dtype, nrec, B, T, H, ldg, ldy, true, g, &ok) == 0 && ok) return 1;
   return tt_gru_fwd_launches(dtype, T, H);
+}
+
+// The row-owning persistent forward (A: FwdArgs, the training form, or InfArgs, the inference form).
+template <typename A>
+static int launch_fwd_seq(const A& a, int nrec, int B, int H, hipStream_t st) {
+  const dim3 grid(tt_ceil_div(B, PR) * nrec);
+  int depth = (H / 64) % 4 == 0 ? 4 : (H / 64) % 2 == 0 ? 2 : 1;
+  depth = std::min(depth, tt::opt(tt::OPT_GRU_DEPTH));
+#define TT_SEQ(D, N) (gru_fwd_seq<D, N, A>)
+  if (depth >= 4 && H == 512) hipLaunchKernelGGL(TT_SEQ(4, 8), grid, dim3(PNT), 0, st, a);
+  else if (depth >= 4 && H == 256) hipLaunchKernelGGL(TT_SEQ(4, 4), grid, dim3(PNT), 0, st, a);
+  else if (depth >= 4) hipLaunchKernelGGL(TT_SEQ(4, 0), grid, dim3(PNT), 0, st, a);
+  else if (depth == 2 && H == 512) hipLaunchKernelGGL(TT_SEQ(2, 8), grid, dim3(PNT), 0, st, a);
+  else if (depth == 2 && H == 256) hipLaunchKernelGGL(TT_SEQ(2, 4), grid, dim3(PNT), 0, st, a);
+  else if (depth == 2) hipLaunchKernelGGL(TT_SEQ(2, 0), grid, dim3(PNT), 0, st, a);
+  else if (H == 512) hipLaunchKernelGGL(TT_SEQ(1, 8), grid, dim3(PNT), 0, st, a);
+  else if (H == 256) hipLaunchKernelGGL(TT_SEQ(1, 4), grid, dim3(PNT), 0, st, a);
+  else hipLaunchKernelGGL(TT_SEQ(1, 0), grid, dim3(PNT), 0, st, a);
+#undef TT_SEQ
+  TT_CHECK_LAUNCH("gru_fwd_seq");
+  return 0;
+}
+
+// The per-step forward, T launches (A as above).
+template <typename A>
+static int launch_fwd_steps(int dtype, A a, int nrec, int B, int T, int H, long ldg, long ldy, hipStream_t st) {
+  const int esz = dtype == TT_DT_BF16 ? 2 : 4;
+  // 256-row tiles where they still give >= 2 workgroups per CU (option gru_fwd_step_rows
+  // 128 / 256 forces one)
+  int bmr = tt::opt(tt::OPT_GRU_FWD_STEP_ROWS);
+  if (bmr != 128 && bmr != 256)
+    bmr = (long)tt_ceil_div(H, 64) * tt_ceil_div(B, 256) * nrec >= 512 ? 256 : 128;
+  // the step kernel's S / X1 byte offsets are int relative to the tile's first row
+  const long span = (long)T * std::max({4L * H, ldy, ldg}) * esz;
+  if (bmr == 256 && 256L * span >= (1L << 31)) bmr = 128;
+  TT_CHECK_ARG((long)bmr * span < (1L << 31), "tt_gru_fwd: tile byte offsets exceed 2 GiB (B tile %d)", bmr);
+  dim3 grid(tt_ceil_div(H, 64) * tt_ceil_div(B, bmr) * nrec);
+  // 128-row tiles: a 3-stage product ring when option gru_step_ring >= 3 and the grid is
+  // one workgroup per CU at most (120 KiB of LDS: at two per CU the second workgroup's
+  // overlap is worth more, configs[4] 49.7 vs 85.9 ms per layer, profiles/r04_gru_fwd_ring_c4_s.txt)
+  XcDev* xd = nullptr;
+  TT_PROPAGATE(xc_device(&xd));
+  const bool ring = tt::opt(tt::OPT_GRU_STEP_RING) >= 3 && (long)grid.x <= xd->cus;
+#define TT_STEP(T, R, NS) (gru_fwd_step<T, R, NS, A>)
+  for (int s = 0; s < T; ++s) {
+    a.s = s;
+    if (dtype == TT_DT_BF16) {
+      if (bmr == 256) hipLaunchKernelGGL(TT_STEP(bf16_t, 256, 2), grid, dim3(512), 0, st, a);
+      else if (ring) hipLaunchKernelGGL(TT_STEP(bf16_t, 128, 3), grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL(TT_STEP(bf16_t, 128, 2), grid, dim3(256), 0, st, a);
+    } else {
+      if (bmr == 256) hipLaunchKernelGGL(TT_STEP(float, 256, 2), grid, dim3(512), 0, st, a);
+      else if (ring) hipLaunchKernelGGL(TT_STEP(float, 128, 3), grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL(TT_STEP(float, 128, 2), grid, dim3(256), 0, st, a);
+    }
+    TT_CHECK_LAUNCH("gru_fwd_step");
+  }
+#undef TT_STEP
+  return 0;
 }
 
 extern "C" int tt_gru_fwd(int dtype, const tt_gru_fwd_rec* recs, int nrec, int B, int T, int H, long ldg,
@@ -2380,52 +2532,59 @@ extern "C" int tt_gru_fwd(int dtype, const tt_gru_fwd_rec* recs, int nrec, int B
     TT_PROPAGATE(gru_fwd_xc_launch(a, nrec, B, T, H, ldg, ldy, ws, ws_bytes, st, &used));
     if (used) return 0;
   }
-  if (gru_fwd_persistent(dtype, H)) {
-    const dim3 grid(tt_ceil_div(B, PR) * nrec);
-    int depth = (H / 64) % 4 == 0 ? 4 : (H / 64) % 2 == 0 ? 2 : 1;
-    depth = std::min(depth, tt::opt(tt::OPT_GRU_DEPTH));
-    if (depth >= 4 && H == 512) hipLaunchKernelGGL((gru_fwd_seq<4, 8>), grid, dim3(PNT), 0, st, a);
-    else if (depth >= 4 && H == 256) hipLaunchKernelGGL((gru_fwd_seq<4, 4>), grid, dim3(PNT), 0, st, a);
-    else if (depth >= 4) hipLaunchKernelGGL((gru_fwd_seq<4, 0>), grid, dim3(PNT), 0, st, a);
-    else if (depth == 2 && H == 512) hipLaunchKernelGGL((gru_fwd_seq<2, 8>), grid, dim3(PNT), 0, st, a);
-    else if (depth == 2 && H == 256) hipLaunchKernelGGL((gru_fwd_seq<2, 4>), grid, dim3(PNT), 0, st, a);
-    else if (depth == 2) hipLaunchKernelGGL((gru_fwd_seq<2, 0>), grid, dim3(PNT), 0, st, a);
-    else if (H == 512) hipLaunchKernelGGL((gru_fwd_seq<1, 8>), grid, dim3(PNT), 0, st, a);
-    else if (H == 256) hipLaunchKernelGGL((gru_fwd_seq<1, 4>), grid, dim3(PNT), 0, st, a);
-    else hipLaunchKernelGGL((gru_fwd_seq<1, 0>), grid, dim3(PNT), 0, st, a);
-    TT_CHECK_LAUNCH("gru_fwd_seq");
-    return 0;
+  if (gru_fwd_persistent(dtype, H)) return launch_fwd_seq(a, nrec, B, H, st);
+  return launch_fwd_steps(dtype, a, nrec, B, T, H, ldg, ldy, st);
+}
+
+// ---- inference forward: no saved pre-activations, optionally only the final state ------
+extern "C" long tt_gru_infer_scratch_size(int dtype, int B, int T, int H, int final_only) {
+  if ((dtype != TT_DT_F32 && dtype != TT_DT_BF16) || B <= 0 || T <= 0 || H <= 0) return 0;
+  if (gru_fwd_persistent(dtype, H)) return 0;  // the state never leaves the chip
+  // per-step kernel: the fp32 state [2][B][H], and without Y the image of h it multiplies
+  const long esz = dtype == TT_DT_BF16 ? 2 : 4;
+  return 2L * B * H * 4 + (final_only ? 2L * B * H * esz : 0);
+}
+
+extern "C" int tt_gru_fwd_infer(int dtype, const tt_gru_infer_rec* recs, int nrec, int B, int T, int H, long ldg,
+                                long ldy, long ldf, void* ws, long ws_bytes, void* stream) {
+  TT_CHECK_ARG(dtype == TT_DT_F32 || dtype == TT_DT_BF16, "tt_gru_fwd_infer: bad dtype");
+  TT_CHECK_ARG(nrec >= 1 && nrec <= 4, "tt_gru_fwd_infer: nrec %d", nrec);
+  TT_CHECK_ARG(B > 0 && T > 0 && H > 0, "tt_gru_fwd_infer: bad shape");
+  TT_CHECK_ARG(ws_bytes >= 0 && (ws != nullptr || ws_bytes == 0), "tt_gru_fwd_infer: ws / ws_bytes");
+  const int esz = dtype == TT_DT_BF16 ? 2 : 4;
+  TT_CHECK_ARG(H % 8 == 0 && (ldy * esz) % 16 == 0, "tt_gru_fwd_infer: H=%d (multiple of 8)/ldy=%ld misaligned", H, ldy);
+  TT_CHECK_ARG(tt_ceil_div(B, 128) <= 65535, "tt_gru_fwd_infer: B too large");
+  TT_CHECK_ARG(128L * T * std::max({4L * H, ldy, ldg}) * esz < (1L << 31),
+               "tt_gru_fwd_infer: tile byte offsets exceed 2 GiB");
+  const bool has_y = recs[0].y != nullptr, has_f = recs[0].hfinal != nullptr;
+  TT_CHECK_ARG(has_y || has_f, "tt_gru_fwd_infer: neither y nor hfinal given");
+  TT_CHECK_ARG(!has_f || (ldf >= H && (ldf * esz) % 16 == 0 && 256L * ldf * esz < (1L << 31)),
+               "tt_gru_fwd_infer: ldf=%ld misaligned or below H", ldf);
+  const bool persistent = gru_fwd_persistent(dtype, H);
+  const long state = 2L * B * H * 4;
+  InfArgs a{};
+  for (int i = 0; i < nrec; ++i) {
+    const tt_gru_infer_rec& r = recs[i];
+    TT_CHECK_ARG(r.g && r.whh && r.bhn, "tt_gru_fwd_infer: null pointer in rec %d", i);
+    TT_CHECK_ARG((r.y != nullptr) == has_y && (r.hfinal != nullptr) == has_f,
+                 "tt_gru_fwd_infer: rec %d disagrees with rec 0 on y / hfinal", i);
+    TT_CHECK_ARG(persistent || (r.scratch && ((uintptr_t)r.scratch & 15) == 0),
+                 "tt_gru_fwd_infer: rec %d needs 16-byte aligned scratch (tt_gru_infer_scratch_size)", i);
+    a.r[i] = FwdRec{r.g, r.whh, r.bhn, r.y, nullptr, nullptr, static_cast<float*>(r.scratch), r.dir, 0u, 0, 0u};
+    for (int k = nrec; k < 4; ++k) a.hfin[k] = a.himg[k] = nullptr;
+    a.hfin[i] = r.hfinal;
+    a.himg[i] = r.scratch && !has_y ? static_cast<char*>(r.scratch) + state : nullptr;
   }
-  // 256-row tiles where they still give >= 2 workgroups per CU (option gru_fwd_step_rows
-  // 128 / 256 forces one)
-  int bmr = tt::opt(tt::OPT_GRU_FWD_STEP_ROWS);
-  if (bmr != 128 && bmr != 256)
-    bmr = (long)tt_ceil_div(H, 64) * tt_ceil_div(B, 256) * nrec >= 512 ? 256 : 128;
-  // the step kernel's S / X1 byte offsets are int relative to the tile's first row
-  const long span = (long)T * std::max({4L * H, ldy, ldg}) * esz;
-  if (bmr == 256 && 256L * span >= (1L << 31)) bmr = 128;
-  TT_CHECK_ARG((long)bmr * span < (1L << 31), "tt_gru_fwd: tile byte offsets exceed 2 GiB (B tile %d)", bmr);
-  dim3 grid(tt_ceil_div(H, 64) * tt_ceil_div(B, bmr) * nrec);
-  // 128-row tiles: a 3-stage product ring when option gru_step_ring >= 3 and the grid is
-  // one workgroup per CU at most (120 KiB of LDS: at two per CU the second workgroup's
-  // overlap is worth more, configs[4] 49.7 vs 85.9 ms per layer, profiles/r04_gru_fwd_ring_c4_s.txt)
-  XcDev* xd = nullptr;
-  TT_PROPAGATE(xc_device(&xd));
-  const bool ring = tt::opt(tt::OPT_GRU_STEP_RING) >= 3 && (long)grid.x <= xd->cus;
-  for (int s = 0; s < T; ++s) {
-    a.s = s;
-    if (dtype == TT_DT_BF16) {
-      if (bmr == 256) hipLaunchKernelGGL((gru_fwd_step<bf16_t, 256>), grid, dim3(512), 0, st, a);
-      else if (ring) hipLaunchKernelGGL((gru_fwd_step<bf16_t, 128, 3>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((gru_fwd_step<bf16_t, 128>), grid, dim3(256), 0, st, a);
-    } else {
-      if (bmr == 256) hipLaunchKernelGGL((gru_fwd_step<float, 256>), grid, dim3(512), 0, st, a);
-      else if (ring) hipLaunchKernelGGL((gru_fwd_step<float, 128, 3>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((gru_fwd_step<float, 128>), grid, dim3(256), 0, st, a);
-    }
-    TT_CHECK_LAUNCH("gru_fwd_step");
+  a.B = B; a.T = T; a.H = H; a.ldg = ldg; a.ldy = ldy; a.ldf = ldf;
+  a.inv_keep = 1.0f;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == TT_DT_BF16) {
+    bool used = false;
+    TT_PROPAGATE(gru_fwd_xc_launch(a, nrec, B, T, H, ldg, ldy, ws, ws_bytes, st, &used));
+    if (used) return 0;
   }
-  return 0;
+  if (persistent) return launch_fwd_seq(a, nrec, B, H, st);
+  return launch_fwd_steps(dtype, a, nrec, B, T, H, ldg, ldy, st);
 }
 
 // option gru_step_ring: LDS stages of the per-step backward's product (2: double buffer)

@@ -26,7 +26,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, dist, ops, timing
-from ._lib import GruBwdRec, GruFwdRec, HeadBwdIO, HeadFwdIO, call, dtype_code, stream_ptr
+from ._lib import GruBwdRec, GruFwdRec, GruInferRec, HeadBwdIO, HeadFwdIO, call, dtype_code, stream_ptr
 
 PARAMS_PER_TOWER = 22
 LN_EPS = 1e-5
@@ -346,7 +346,8 @@ def _gru_layer_fwd(cfg, xs, K, ldx, packs, layer, B, T, seeds, want_x1, ws):
     per = esz * (8 + (1 if want_x1 else 0)) + (0 if nl == 1 else esz + 8)
     if nl == 1 and ws is not None:
         form = "gru_fwd_xs" if H == 512 and _xs_selected() else "gru_fwd_xcp"
-        kname = f"{form}<{H}, {'true' if want_x1 and cfg.drop_p > 0 else 'false'}>"
+        # a prefix of the name: the instance's last template argument is its argument struct
+        kname = f"{form}<{H}, {'true' if want_x1 and cfg.drop_p > 0 else 'false'}"
     elif nl == 1:
         kname = "gru_fwd_seq<"
     else:
@@ -357,6 +358,104 @@ def _gru_layer_fwd(cfg, xs, K, ldx, packs, layer, B, T, seeds, want_x1, ws):
              ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream_ptr(dev))
     del G
     return Y, X1, S
+
+
+def _gru_layer_infer(cfg, xs, K, ldx, packs, layer, B, T, ws, final_only):
+    """Input projection + one bidirectional GRU layer without backward state
+    (tt_gru_fwd_infer): no saved pre-activations, no dropout copy. Returns the layer output
+    Y [B*T, 2H] per tower, or with final_only the final states cat(h_fwd at T-1, h_rev at 0)
+    [B, 2H] per tower, which the kernels write in place of Y."""
+    n, H, dt, dev = cfg.ntowers, cfg.H, cfg.dtype, xs[0].device
+    BT = B * T
+    lib = _lib.load()
+    G = [_alloc((BT, 6 * H), dt, dev) for _ in range(n)]
+    esz = 2 if dt == torch.bfloat16 else 4
+    kr = cfg.E if layer == 0 else K
+    with timing.region(f"input_proj_infer_l{layer}", 1, 2.0 * BT * 6 * H * kr * n,
+                       float(n * esz * (BT * kr + 6 * H * kr + BT * 6 * H))):
+        ops.gemm(xs, [p.wih[layer] for p in packs], G, m=BT, n=6 * H, k=K, lda=ldx, ldb=K, ldc=6 * H,
+                 a_kouter=False, b_kouter=False, dtype=dt, out_dtype=dt, bias=[p.bias[layer] for p in packs])
+    out = [_alloc((B, 2 * H) if final_only else (BT, 2 * H), dt, dev) for _ in range(n)]
+    nb = lib.tt_gru_infer_scratch_size(dtype_code(dt), B, T, H, int(final_only))
+    scr = _alloc((2 * n, nb), torch.uint8, dev) if nb > 0 else None
+    recs = (GruInferRec * (2 * n))()
+    for ti in range(n):
+        for d in range(2):
+            r = recs[ti * 2 + d]
+            r.g = G[ti][:, d * 3 * H:].data_ptr()
+            r.whh = packs[ti].whh[layer][d].data_ptr()
+            r.bhn = packs[ti].bhn[layer][d].data_ptr()
+            r.y = None if final_only else out[ti][:, d * H:].data_ptr()
+            r.hfinal = out[ti][:, d * H:].data_ptr() if final_only else None
+            r.scratch = scr[ti * 2 + d].data_ptr() if scr is not None else None
+            r.dir = d
+    # algorithmic bytes per (row, unit, step): gates 3 (+ h 1 when Y is written) elements of
+    # dt; the per-step kernel also re-reads h_{s-1} and moves the fp32 state through HBM
+    nl = lib.tt_gru_fwd_launches_for(dtype_code(dt), 2 * n, B, T, H, 6 * H, 2 * H) if ws is not None \
+        else lib.tt_gru_fwd_launches(dtype_code(dt), T, H)
+    per = esz * (3 if final_only else 4) + (0 if nl == 1 else esz * (2 if final_only else 1) + 8)
+    if nl == 1 and ws is not None:
+        kname = f"{'gru_fwd_xs' if H == 512 and _xs_selected() else 'gru_fwd_xcp'}<{H}, false, (anonymous namespace)::InfArgs>"
+    elif nl == 1:
+        kname = "gru_fwd_seq<"
+    else:
+        kname = "gru_fwd_step<"
+    with timing.region("gru_infer", nl, 2.0 * B * H * 3 * H * 2 * n * (T - 1), float(B * T * H * 2 * n * per),
+                       kernel=kname):
+        call("tt_gru_fwd_infer", dtype_code(dt), recs, 2 * n, B, T, H, 6 * H, 2 * H, 2 * H,
+             ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream_ptr(dev))
+    return out
+
+
+def towers_infer(cfg: TowerCfg, table, xs, params):
+    """The towers without autograd state, for calls that take no gradient and draw no dropout
+    (eval / no-grad encodes): featurize -> input projection -> layer 0 (no saved state) ->
+    input projection -> layer 1 (no saved state, final states only) -> head. The same kernels'
+    arithmetic as TowersFn.forward with dropout 0, so the outputs are bit-identical to it."""
+    n = cfg.ntowers
+    _lib.require_gpu(*xs, *params)
+    check_gru_status(wait=True)  # every earlier forward's column-split launches
+    dt, E, H, h = cfg.dtype, cfg.E, cfg.H, cfg.h
+    dev = xs[0].device
+    reset_guard_if_reported(dev)
+    B, T = xs[0].shape[0], xs[0].shape[1]
+    for x in xs:
+        if x.shape[0] != B or x.shape[1] != T:
+            raise ValueError("query and doc inputs must share [B, T] in one fused call")
+    Ep = ops.pad_cols(E, dt)
+    npt = cfg.nparams
+    with torch.no_grad():
+        packs = [_packed(params[i * npt:(i + 1) * npt], cfg, Ep, True) for i in range(n)]
+        X0 = [featurize(x, table, Ep, dt) for x in xs]
+        ws = gru_fwd_workspace(2 * n, B, T, H, dt, dev)
+        Y0 = _gru_layer_infer(cfg, X0, Ep, Ep, packs, 0, B, T, ws, False)
+        del X0
+        hfin = _gru_layer_infer(cfg, Y0, 2 * H, 2 * H, packs, 1, B, T, ws, True)
+        del Y0
+        if ws is not None:
+            watch_gru_status(ws, arm=False)  # reported by check_gru_status; never blocks an optimiser step
+        hcat = [f if f.dtype == HEAD_DT else f.to(HEAD_DT) for f in hfin]
+        if cfg.head == "none":
+            return tuple(hcat)
+        outs, keep = [], []
+        io = (HeadFwdIO * n)()
+        for ti in range(n):
+            pk = packs[ti]
+            # p1 / u / mean / rstd: the head kernel's own intermediates, freed on return
+            p1 = _alloc((B, 2 * h), HEAD_DT, dev)
+            u = _alloc((B, 2 * h), HEAD_DT, dev)
+            mean = _alloc((B,), torch.float32, dev)
+            rstd = _alloc((B,), torch.float32, dev)
+            out = _alloc((B, h), torch.float32, dev)
+            q = io[ti]
+            q.w1, q.b1, q.ln_g, q.ln_b = pk.w1.data_ptr(), pk.b1.data_ptr(), pk.ln_g.data_ptr(), pk.ln_b.data_ptr()
+            q.w2, q.b2 = pk.w2.data_ptr(), pk.b2.data_ptr()
+            q.x, q.p1, q.mean, q.rstd, q.u, q.out = (hcat[ti].data_ptr(), p1.data_ptr(), mean.data_ptr(),
+                                                     rstd.data_ptr(), u.data_ptr(), out.data_ptr())
+            outs.append(out)
+            keep += [p1, u, mean, rstd]
+        call("tt_proj_head_fwd", dtype_code(HEAD_DT), io, n, B, h, LN_EPS, stream_ptr(dev))
+        return tuple(outs)
 
 
 def _gru_layer_bwd(cfg, layer, B, T, S, Y, dY, dfinal, packs):
@@ -672,4 +771,8 @@ def run_towers(cfg: TowerCfg, table, xs, params, reduce_group=None, reduce: bool
     # inference (no gradient wanted): the packed compute copies may be reused while the
     # parameters are unchanged (retrieval / serving encode many batches per weight version)
     cache_ok = not (torch.is_grad_enabled() and any(p.requires_grad for p in params))
+    if cache_ok and cfg.drop_p == 0.0:
+        # ... and nothing of the forward is kept for a backward: the inference kernels (a
+        # no-grad call of a model in train() mode still draws dropout, so it stays below)
+        return towers_infer(cfg, table, xs, params)
     return TowersFn.apply(cfg, table, group, cache_ok, *xs, *params)

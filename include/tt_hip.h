@@ -204,9 +204,12 @@ int  tt_gru_fwd_infer(int dtype, const tt_gru_infer_rec* recs, int nrec, int B, 
 long tt_gru_infer_scratch_size(int dtype, int B, int T, int H, int final_only);
 
 /* Backward (BPTT) of tt_gru_fwd. Produces dL/dg (= dgx, feeds dWih, dbih and the
- * layer-input gradient) and dL/dgh (feeds dWhh), plus bias partial sums (one row per
- * 128-row batch tile: tt_gru_bias_rows(B) rows; columns r|z|n|ghn; reduce with tt_colsum:
- * dbih = [0:3H], dbhh = [0:2H] ++ [3H:4H]). */
+ * layer-input gradient) and dL/dgh (feeds dWhh), plus bias partial sums: tt_gru_bias_rows(B)
+ * = ceil(B / 64) rows, one per 64-row batch tile (the smallest backward tile; a kernel on
+ * larger tiles fills one row per tile and leaves the rest zero), columns r|z|n|ghn; reduce
+ * with tt_colsum: dbih = [0:3H], dbhh = [0:2H] ++ [3H:4H].
+ * dy and dfinal are independent: either or both may be given in every kernel family; dfinal
+ * enters dL/dh at the recurrence's last processed step, dy at every step. */
 typedef struct {
   const void* save;    /* [B*T, 4H] from tt_gru_fwd          */
   const void* y;       /* layer output (source of h_{s-1})   */

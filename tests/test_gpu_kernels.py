@@ -1,4 +1,9 @@
-"""Kernel-level parity on the GPU: tt_gemm layouts, GRU layer, head, losses, Adam.
+"""Kernel-level parity on the GPU: tt_gemm (operand layouts, the 256 x 256, persistent,
+B-resident and four-wave kernels, split-K, the shifted GRU operand, bias / dropout epilogues),
+the embedding gather, the one-launch weight pack and Adam. Not here: the GRU layer kernels
+(tt_gru_fwd / tt_gru_bwd, against float64 in test_gpu_gru_ref.py), the projection heads
+(test_gpu_head_ref.py), the losses and mining (test_gpu_infonce_bwd.py, test_gpu_margin.py,
+test_gpu_hardneg.py, test_gpu_search.py).
 
 Reference for every floating-point kernel is plain PyTorch fp32 / fp64 on the CPU
 (the oracle's arithmetic). Tolerances: fp32 kernels rtol 1e-4-ish (accumulation

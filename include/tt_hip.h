@@ -43,7 +43,7 @@ const char* tt_last_error(void);
  * GRU: gru_step, gru_depth, gru_bwd_rows, gru_bwd_big, gru_bwd_streams, gru_bwd_persist,
  * gru_bwd_skew, gru_fwd_step_rows, gru_fwd_xc, gru_fwd_xs, gru_fwd_skew, gru_xc_coop,
  * gru_step_ring; GEMM: gemm_persist, gemm_persist_maxk, gemm_a3, gemm_buf, gemm_bres,
- * bres_rows, gemm_iepi, gemm_order, gemm_skew, gemm_regstage, gemm_stream_out; losses:
+ * bres_rows, bres_form, gemm_iepi, gemm_order, gemm_skew, gemm_regstage, gemm_stream_out; losses:
  * hn_gemm, hn_map, hn_scan_gemm, infonce_flash; diagnostics gru_xc_skip, gru_xc_spins. The authoritative list with
  * defaults is kOpts in two_towers_amd/csrc/tt_gemm.hip. Every variant computes the same
  * function; they exist for A/B measurement and for tests that compare variants.
@@ -122,6 +122,11 @@ int tt_gemm(int dtype, int out_dtype, int a_kouter, int b_kouter, int m, int n, 
 long tt_gemm_ws_size(int m, int n, int nbatch, int splits);
 /* Heuristic split count for a (m, n, k, nbatch) problem. */
 int tt_gemm_pick_splits(int m, int n, int k, int nbatch);
+/* Which B-resident short-K kernel tt_gemm runs a bf16, a_kouter = b_kouter = 0, bias-only,
+ * one-split product of this shape on (16-byte aligned C rows and biases), under the
+ * current options: 0 none (the general kernels), 1 gemm_bres (a panel of B in LDS),
+ * 2 gemm_wreg (B in registers, A rows through an LDS ring; option bres_form 1). */
+int tt_gemm_bres_form(int m, int n, int k, int nbatch, long lda, long ldc);
 
 /* ------------------------------------------------------------------------- GRU */
 /* One bidirectional GRU layer, forward, all time steps (torch nn.GRU semantics:

@@ -44,6 +44,7 @@ constexpr OptDef kOpts[OPT_N] = {
     {"gru_fwd_xs", "TT_GRU_FWD_XS", 1},           {"hn_scan_gemm", "TT_HN_SCAN_GEMM", 0},
     {"gemm_iepi", "TT_GEMM_IEPI", 1},             {"bres_rows", "TT_BRES_ROWS", 32},
     {"hn_scan_v", "TT_HN_SCAN_V", 5},             {"gemm_w4", "TT_GEMM_W4", 0},
+    {"bres_form", "TT_BRES_FORM", 1},
 };
 struct OptTable {
   std::atomic<int> v[OPT_N];
@@ -685,6 +686,186 @@ __global__ __launch_bounds__(RB == 2 ? 512 : 256, 1) void gemm_bres(GemmArgs g, 
       }
     }
   }
+}
+
+// ---- B-resident short-K GEMM, weights in registers (option bres_form 1) ----------------
+// The same product and workgroup -> (row group, batch entry, panel) mapping as gemm_bres,
+// but the B panel never enters LDS: a workgroup covers 512 columns and each of its 8 waves
+// keeps its own 64-column slice of B as MFMA fragments in registers for the whole launch
+// (4 column blocks x NKS k-steps x 16 bytes per lane: 160 registers at K 320, pinned like
+// gru_fwd_xs's wa; 248 VGPRs in all, no scratch). All 8 waves walk the SAME 64-row A tiles,
+// which arrive by LDS-DMA in whole 128-byte lines through a ring of WR_NS slots (K-tile
+// images in the kc_off layout: source address pre-swizzled, destination linear; wave w moves
+// rows 8w..8w+7 of every image), so the only LDS fragment reads are A's, each feeding 4
+// MFMAs, and every A row is fetched from L2 once per workgroup instead of once per wave in
+// 64-byte pieces. A wave's 64 columns are one 128-byte line of a C row: its stores write
+// whole lines (row_pair). The grid is ngrp x (panels x batch) <= 256 workgroups of whole
+// row groups (N 3072, two towers: 21 x 12 = 252).
+// Per tile t: counted wait for this wave's DMAs of tile t, ONE barrier (everyone's DMAs of t
+// landed; everyone's reads of tile t-1 are done), DMAs of tile t+2 into tile t-1's slot, then
+// the MFMAs and the output stores of tile t (two 32-row passes: the accumulators of 64 rows
+// do not fit beside the weights). vmcnt retires in order, so the wait for tile t's DMAs
+// allows exactly what this wave issued after them: the stores of t-2, the DMAs of t+1, the
+// stores of t-1 (fewer in the first two tiles). Every DMA and every store is issued
+// unconditionally (rows past M and tiles past the group's last read zeros / are dropped
+// through the buffer resources' ranges), so those counts are exact. Same MFMA, operand order
+// and k order as gemm_bres: bit-identical.
+#ifndef WR_DIAG  // timing-only diagnostic switches of gemm_wreg (results wrong): 1 no output stores, 2 no A DMAs in the loop
+#define WR_DIAG 0
+#endif
+constexpr int WR_CB = 4;                  // 16-column blocks per wave (3, 384-column panels: 2.28 vs 2.17 ms)
+constexpr int WR_COLS = 8 * 16 * WR_CB;   // panel columns per workgroup
+constexpr int WR_TR = 64;                 // rows per tile (one DMA piece of 8 rows per wave and K-tile image)
+constexpr int WR_NS = 3;                  // ring slots
+constexpr int WR_MAXKS = 10;              // K <= 320: 40 weight fragments of 4 registers
+constexpr int WR_EST = (WR_DIAG & 1) ? 0 : WR_TR * 16 * WR_CB * 2 / 1024;  // output stores per wave and tile
+typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
+typedef float f32x2v __attribute__((ext_vector_type(2)));
+// two fp32 -> one dword of bf16 (one v_cvt_pk_bf16_f32: the rounding of f2bf)
+TT_DEV uint32_t pack2bf(float lo, float hi) {
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2v{lo, hi}, bf16x2v));
+}
+template <int NKS>
+__global__ __launch_bounds__(512, 1) void gemm_wreg(GemmArgs g, int npan, int nbatch) {
+  static_assert(NKS >= 1 && NKS <= WR_MAXKS, "weight slice must fit the register budget");
+  constexpr int NKT = (NKS + 1) / 2;         // 64-deep K-tile images per tile
+  constexpr int IMG = WR_TR * ttg::KTB;      // 8 KiB: one DMA piece (8 rows) per wave
+  constexpr int SLOT = NKT * IMG;
+  constexpr int NDMA = (WR_DIAG & 2) ? 0 : NKT;  // DMAs per wave and tile in the loop
+  // row blocks per pass: the weights leave registers for 32 rows of accumulators, so a tile
+  // is computed in two passes (each with its own stores)
+  constexpr int RB = 2;
+  constexpr int NPASS = WR_TR / (16 * RB);
+  static_assert(WR_NS * SLOT <= 160 * 1024, "ring fits the LDS");
+  __shared__ __attribute__((aligned(16))) char lds[WR_NS * SLOT];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int lr = lane & 15, q = lane >> 4;
+  const int ptot = npan * nbatch;
+  const int bid = ttg::xcd_remap(blockIdx.x, gridDim.x);
+  const int ngrp = gridDim.x / ptot;
+  const int gi = bid / ptot, p = bid % ptot;
+  const int bi = p / npan, n0 = (p % npan) * WR_COLS + wave * (16 * WR_CB);  // this wave's first column
+  const bf16_t* A = static_cast<const bf16_t*>(g.a[bi]);
+  const bf16_t* Bm = static_cast<const bf16_t*>(g.b[bi]);
+  bf16_t* C = static_cast<bf16_t*>(g.c[bi]);
+  const float* bias = g.bias[bi];
+  // this group's rows in WR_TR-row tiles
+  const int mg = ((g.M + ngrp - 1) / ngrp + WR_TR - 1) / WR_TR * WR_TR;
+  const int g0 = gi * mg;
+  const int rows = max(0, min(mg, g.M - g0));
+  const int ntl = (rows + WR_TR - 1) / WR_TR;
+  // A through a buffer resource that ends with the group's last valid element: rows past M
+  // (and a phantom tile's offset 2^31) read zeros
+  const ttg::tt_rsrc4 ra = ttg::make_rsrc4(A + (long)g0 * g.lda, rows > 0 ? (uint32_t)(((long)(rows - 1) * g.lda + g.K) * 2) : 0u);
+  const uint32_t base = __builtin_amdgcn_readfirstlane(ttg::lds_addr_of(lds));
+  // lane -> (row, chunk slot) of this wave's 1 KiB piece; slot s of row r holds chunk s ^ ((r >> 1) & 7)
+  const int prow = wave * 8 + (lane >> 3);
+  const uint32_t voff0 = (uint32_t)(prow * (int)g.lda * 2 + (((lane & 7) ^ ((prow >> 1) & 7)) << 4));
+  const uint32_t tstep = (uint32_t)(WR_TR * (int)g.lda * 2);
+  auto issue = [&](int t) {
+    const uint32_t rv = t < ntl ? voff0 + (uint32_t)t * tstep : 0x80000000u;
+    const uint32_t dst = base + (uint32_t)(t % WR_NS) * SLOT + (uint32_t)wave * 1024u;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) ttg::dma16_buf(ra, rv + kt * ttg::KTB, 0u, dst + kt * IMG);
+  };
+  issue(0);
+  issue(1);
+  // the wave's slice of B as fragments (B first operand: lane = column lr of block j, k = 32 ks + 8 q ..)
+  tt_u32x4 wa[WR_CB][NKS];
+#pragma unroll
+  for (int j = 0; j < WR_CB; ++j)
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks)
+      wa[j][ks] = *reinterpret_cast<const tt_u32x4*>(Bm + (long)(n0 + 16 * j + lr) * g.ldb + ks * 32 + q * 8);
+  float bv[WR_CB][4];
+#pragma unroll
+  for (int j = 0; j < WR_CB; ++j) {
+    const float4 b4 = bias ? *reinterpret_cast<const float4*>(bias + n0 + 16 * j + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+    bv[j][0] = b4.x; bv[j][1] = b4.y; bv[j][2] = b4.z; bv[j][3] = b4.w;
+  }
+#pragma unroll
+  for (int j = 0; j < WR_CB; ++j)
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) asm volatile("" : "+v"(wa[j][ks]));
+  const __amdgpu_buffer_rsrc_t rc = tt_rsrc(C + (long)g0 * g.ldc);
+  for (int t = 0; t < ntl; ++t) {
+    // this wave's DMAs of tile t have landed (younger: see the header)
+    if (t == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");
+    else if (t == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA + WR_EST) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA + 2 * WR_EST) : "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's reads of tile t-1
+    __builtin_amdgcn_s_barrier();
+    if (NDMA) issue(t + 2);  // into tile t-1's slot
+    __builtin_amdgcn_sched_barrier(0);
+    const char* slot = lds + (t % WR_NS) * SLOT;
+    // a store of 16 bytes at (row of the tile, column); always issued: a row past M is dropped
+    // through the resource's range (offset 2^31)
+    auto put = [&](int row, int col, uint4 v) {
+      const int gr = t * WR_TR + row;
+      const uint32_t off = gr < rows ? (uint32_t)(((long)gr * g.ldc + col) * 2) : 0x80000000u;
+#if WR_DIAG & 1  // timing only: no stores (the packed values stay live)
+      asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w), "v"(off));
+#else
+      st16_buf(rc, off, 0, v);
+#endif
+    };
+#pragma unroll
+    for (int ps = 0; ps < NPASS; ++ps) {
+      const int r0 = ps * 16 * RB;  // the pass's first row of the tile
+      f32x4 acc[RB][WR_CB];
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+        for (int j = 0; j < WR_CB; ++j) acc[rb][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      uint4 a[2][RB];
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb) a[0][rb] = ttg::frag<bf16_t, false>(slot, r0 + 16 * rb, 0);
+#pragma unroll
+      for (int ks = 0; ks < NKS; ++ks) {
+        if (ks + 1 < NKS) {
+#pragma unroll
+          for (int rb = 0; rb < RB; ++rb)
+            a[(ks + 1) & 1][rb] = ttg::frag<bf16_t, false>(slot + ((ks + 1) >> 1) * IMG, r0 + 16 * rb, (ks + 1) & 1);
+        }
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+          for (int j = 0; j < WR_CB; ++j)
+            acc[rb][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8v, wa[j][ks]),
+                                                                 __builtin_bit_cast(bf16x8v, a[ks & 1][rb]), acc[rb][j], 0, 0, 0);
+        // one k-step per scheduling region (the fragment reads stay one step ahead, no more)
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      // epilogue: acc[rb][j][e] = C(row r0 + 16 rb + lr, col n0 + 16 j + 4 q + e); bias, bf16, then
+      // 16 bytes per lane by v_permlane16_swap
+      uint32_t w[RB][WR_CB][2];
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+        for (int j = 0; j < WR_CB; ++j) {
+          const f32x4 c = acc[rb][j];
+          w[rb][j][0] = pack2bf(c[0] + bv[j][0], c[1] + bv[j][1]);
+          w[rb][j][1] = pack2bf(c[2] + bv[j][2], c[3] + bv[j][3]);
+        }
+      // column blocks 2 jp, 2 jp + 1 of row block rb exchanged (as gemm_bres): lane group q holds
+      // columns 16 (2 jp + (q & 1)) + 8 (q >> 1) .. + 7 of row lr
+      auto pair = [&](int rb, int jp) {
+        const auto s0 = __builtin_amdgcn_permlane16_swap(w[rb][2 * jp][0], w[rb][2 * jp + 1][0], false, false);
+        const auto s1 = __builtin_amdgcn_permlane16_swap(w[rb][2 * jp][1], w[rb][2 * jp + 1][1], false, false);
+        return make_uint4(s0[0], s1[0], s0[1], s1[1]);
+      };
+      // the wave's 128 bytes of a row in whole lines: row_pair, 8 rows x 128 B per store
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb) {
+        uint4 da, db;
+        row_pair(pair(rb, 0), pair(rb, 1), da, db);
+        const int row = r0 + 16 * rb + (lr & 7), cs = n0 + 16 * (q & 1) + 8 * (q >> 1) + (lr & 8 ? 32 : 0);
+        put(row, cs, da);
+        put(row + 8, cs, db);
+      }
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing DMAs land before the LDS is released
 }
 
 // ---- persistent 256x256 GEMM: one workgroup per CU walks tiles w, w+nwg, ... and the
@@ -1430,24 +1611,48 @@ __global__ __launch_bounds__(256, 1) void gemm_w4(GemmArgs g, int ntm, int ntn) 
   }
 }
 
-// gemm_bres where it applies (bf16 NT, bias only, N % 192 == 0, short K): returns true if launched
+// Which B-resident kernel a bf16 NT bias-only product of this shape runs on (operands aligned,
+// no split-K): 0 none, 1 gemm_bres (panel in LDS), 2 gemm_wreg (weights in registers).
+// gemm_wreg (option bres_form 1, 32-row setting of bres_rows): N in whole 512-column panels,
+// K <= 320, at least a quarter tile of rows per row group; everything else the B-resident
+// class covers keeps gemm_bres.
+int bres_form_for(int M, int N, int K, int nbatch, long lda, long ldc) {
+  if (tt::opt(tt::OPT_GEMM_BRES) == 0 || K % 32 || K < 32 || K > 384 || (lda * 2) % 16) return 0;
+  if ((long)M * lda * 2 >= (1L << 31)) return 0;
+  constexpr int nwg = 256;
+  if (tt::opt(tt::OPT_BRES_FORM) == 1 && tt::opt(tt::OPT_BRES_ROWS) != 64 && N % WR_COLS == 0 && K <= 32 * WR_MAXKS) {
+    const int ptot = N / WR_COLS * nbatch;
+    if (ptot <= nwg) {
+      const int ngrp = nwg / ptot;  // whole row groups: ngrp * ptot <= 256 workgroups
+      const long mg = ((long)(M + ngrp - 1) / ngrp + WR_TR - 1) / WR_TR * WR_TR;
+      if ((long)M >= (long)ngrp * (WR_TR / 4) && (mg * ldc + N) * 2 < (1L << 31)) return 2;
+    }
+  }
+  if (N % BR_COLS) return 0;
+  const int ptot = N / BR_COLS * nbatch;
+  if (ptot > nwg || nwg % ptot) return 0;
+  if ((long)M < (long)(nwg / ptot) * 256) return 0;
+  return 1;
+}
+
+// gemm_bres / gemm_wreg where they apply (bf16 NT, bias only, short K): returns true if launched
 template <typename T, typename TO>
 bool try_bres(int akout, int bkout, bool shift, const GemmArgs& g, int nbatch, hipStream_t st, int* rc) {
   *rc = 0;
   if constexpr (!std::is_same<T, bf16_t>::value || !std::is_same<TO, bf16_t>::value) {
     return false;
   } else {
-    if (tt::opt(tt::OPT_GEMM_BRES) == 0 || akout || bkout || shift || g.splits != 1 || g.beta || g.relu ||
-        g.drop_thresh || g.alpha != 1.f || g.force_regstage)
+    if (akout || bkout || shift || g.splits != 1 || g.beta || g.relu || g.drop_thresh || g.alpha != 1.f ||
+        g.force_regstage || !g.vec_ok)
       return false;
-    if (g.N % BR_COLS || g.K % 32 || g.K < 32 || g.K > 384 || !g.vec_ok || (g.lda * 2) % 16) return false;
     for (int b = 0; b < nbatch; ++b)
       if (g.bias[b] && (uintptr_t)g.bias[b] % 16) return false;
-    const int npan = g.N / BR_COLS, ptot = npan * nbatch, nwg = 256;
-    if (ptot > nwg || nwg % ptot) return false;
-    if ((long)g.M < (long)(nwg / ptot) * 256 || (long)g.M * g.lda * 2 >= (1L << 31)) return false;
+    const int form = bres_form_for(g.M, g.N, g.K, nbatch, g.lda, g.ldc);
+    if (form == 0) return false;
     const bool r64 = tt::opt(tt::OPT_BRES_ROWS) == 64;
-    const dim3 grid(nwg), blk(r64 ? 256 : 512);
+    const int npan = g.N / (form == 2 ? WR_COLS : BR_COLS);
+    const int nwg = form == 2 ? npan * nbatch * (256 / (npan * nbatch)) : 256;
+    const dim3 grid(nwg), blk(form == 1 && r64 ? 256 : 512);
     switch (g.K / 32) {
 #define TT_BR(n)                                                                   \
   case n:                                                                          \
@@ -1456,13 +1661,23 @@ bool try_bres(int akout, int bkout, bool shift, const GemmArgs& g, int nbatch, h
     else                                                                           \
       hipLaunchKernelGGL((gemm_bres<n, 2>), grid, blk, 0, st, g, npan, nbatch);    \
     break;
-      TT_BR(1) TT_BR(2) TT_BR(3) TT_BR(4) TT_BR(5) TT_BR(6) TT_BR(7) TT_BR(8) TT_BR(9) TT_BR(10) TT_BR(11) TT_BR(12)
+#define TT_WR(n)                                                                   \
+  case n:                                                                          \
+    if (form == 2)                                                                 \
+      hipLaunchKernelGGL((gemm_wreg<n>), grid, blk, 0, st, g, npan, nbatch);       \
+    else if (r64)                                                                  \
+      hipLaunchKernelGGL((gemm_bres<n, 4>), grid, blk, 0, st, g, npan, nbatch);    \
+    else                                                                           \
+      hipLaunchKernelGGL((gemm_bres<n, 2>), grid, blk, 0, st, g, npan, nbatch);    \
+    break;
+      TT_WR(1) TT_WR(2) TT_WR(3) TT_WR(4) TT_WR(5) TT_WR(6) TT_WR(7) TT_WR(8) TT_WR(9) TT_WR(10) TT_BR(11) TT_BR(12)
+#undef TT_WR
 #undef TT_BR
       default: return false;
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
-      tt::set_error("gemm_bres: %s", hipGetErrorString(e));
+      tt::set_error("%s: %s", form == 2 ? "gemm_wreg" : "gemm_bres", hipGetErrorString(e));
       *rc = (int)e;
     }
     return true;
@@ -1568,6 +1783,10 @@ int tt::tt_hn_scan_gemm(const void* q, long bq, const void* d, long nd, int h, l
                      dim3((unsigned)std::min<long>(ntiles, 256)), dim3(512), 0, st, g, (int)ntiles);
   TT_CHECK_LAUNCH("gemm_persist (hard-negative scan)");
   return 0;
+}
+
+extern "C" int tt_gemm_bres_form(int m, int n, int k, int nbatch, long lda, long ldc) {
+  return bres_form_for(m, n, k, nbatch, lda, ldc);
 }
 
 extern "C" long tt_gemm_ws_size(int m, int n, int nbatch, int splits) {

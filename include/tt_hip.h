@@ -43,7 +43,7 @@ const char* tt_last_error(void);
  * GRU: gru_step, gru_depth, gru_bwd_rows, gru_bwd_big, gru_bwd_streams, gru_bwd_persist,
  * gru_bwd_skew, gru_fwd_step_rows, gru_fwd_xc, gru_fwd_xs, gru_fwd_skew, gru_xc_coop,
  * gru_step_ring; GEMM: gemm_persist, gemm_persist_maxk, gemm_a3, gemm_buf, gemm_bres,
- * bres_rows, bres_form, gemm_iepi, gemm_order, gemm_skew, gemm_regstage, gemm_stream_out; losses:
+ * bres_rows, bres_form, wgrad_tall, gemm_iepi, gemm_order, gemm_skew, gemm_regstage, gemm_stream_out; losses:
  * hn_gemm, hn_map, hn_scan_gemm, infonce_flash; diagnostics gru_xc_skip, gru_xc_spins. The authoritative list with
  * defaults is kOpts in two_towers_amd/csrc/tt_gemm.hip. Every variant computes the same
  * function; they exist for A/B measurement and for tests that compare variants.
@@ -118,6 +118,14 @@ int tt_gemm(int dtype, int out_dtype, int a_kouter, int b_kouter, int m, int n, 
             const tt_gemm_batch* batch, int nbatch, long lda, long ldb, long ldc, float alpha,
             int beta_accum, int relu, int seq_t, uint32_t drop_seed, float drop_p, int splits,
             float* splitk_ws, void* stream);
+/* tt_gemm with C stored transposed when c_trans != 0: C_b[n][m] with ldc >= m (bias still
+ * per n). The split-K reduction writes it, summing the slices in the same order, so the
+ * values are those of tt_gemm: it needs splits > 1 after tt_gemm's clamping to the K-tiles
+ * (an error otherwise). The layer-0 dW_ih, computed as X0^T dG, lands as [3H, Ep]. */
+int tt_gemm_ct(int dtype, int out_dtype, int a_kouter, int b_kouter, int m, int n, int k,
+               const tt_gemm_batch* batch, int nbatch, long lda, long ldb, long ldc, float alpha,
+               int beta_accum, int relu, int seq_t, uint32_t drop_seed, float drop_p, int splits,
+               float* splitk_ws, int c_trans, void* stream);
 /* fp32 elements of splitk_ws: the split partials for splits > 1, else 0. */
 long tt_gemm_ws_size(int m, int n, int nbatch, int splits);
 /* Heuristic split count for a (m, n, k, nbatch) problem. */
@@ -127,6 +135,12 @@ int tt_gemm_pick_splits(int m, int n, int k, int nbatch);
  * current options: 0 none (the general kernels), 1 gemm_bres (a panel of B in LDS),
  * 2 gemm_wreg (B in registers, A rows through an LDS ring; option bres_form 1). */
 int tt_gemm_bres_form(int m, int n, int k, int nbatch, long lda, long ldc);
+/* Whether tt_gemm runs a product of this shape, under the current options, on gemm_tall
+ * (option wgrad_tall: one 320-row tile per 256-column panel; bf16 K-outer operands, fp32
+ * out, 256 < m <= 320): 1, else 0 (the general kernels). splits as passed to tt_gemm;
+ * extras: bit 0 bias, 1 relu, 2 dropout, 3 bshift, 4 a_split, 5 beta_accum. */
+int tt_gemm_tall_form(int dtype, int out_dtype, int a_kouter, int b_kouter, int m, int n, int k, long lda,
+                      long ldb, int splits, int extras);
 
 /* ------------------------------------------------------------------------- GRU */
 /* One bidirectional GRU layer, forward, all time steps (torch nn.GRU semantics:

@@ -16,6 +16,8 @@ SHAPES = {  # name: (m, n, k, a_kouter, b_kouter, nbatch, out_bf16)
     "wgrad_ih1": (1536, 1024, 524288, 1, 1, 4, 0),
     "wgrad_ih0": (1536, 320, 524288, 1, 1, 4, 0),  # N = Ep 320: two 256-column tiles, the second a quarter full
     "wgrad_hh": (1536, 512, 524288, 1, 1, 4, 0),
+    # the step's layer-0 dW_ih dispatch: dW_ih^T = X0^T dG with the step's own strides (run_step_t)
+    "wgrad_ih0_t": (320, 1536, 524288, 1, 1, 4, 0),
     "square8k": (8192, 8192, 8192, 0, 0, 1, 1),
     # diagnostics: the round-1 16-byte padding; the l1 FLOPs with a B small enough for L2
     "input_proj_l0_k304": (524288, 3072, 304, 0, 0, 2, 1),
@@ -34,9 +36,26 @@ for _k in (128, 192, 320, 512, 768, 1024, 1536):
 NO_BIAS = False
 
 
+def run_step_t(name, iters):
+    """wgrad_ih0_t: A = X0 [K, 320] per tower (ld 320), B = the 1536-column gate blocks of a
+    direction at columns 0 and 1536 of a tower's dG [K, 4096]; (tower, direction) problems."""
+    m, n, k, ak, bk, nb, obf = SHAPES[name]
+    dt = torch.bfloat16
+    X0 = [torch.randn(k, m, device="cuda").to(dt) for _ in range(nb // 2)]
+    dG = [torch.randn(k, 4096, device="cuda").to(dt) for _ in range(nb // 2)]
+    A = [X0[i // 2] for i in range(nb)]
+    B = [dG[i // 2][:, (i % 2) * n:] for i in range(nb)]
+    C = [torch.empty(m, n, device="cuda", dtype=torch.float32) for _ in range(nb)]
+    return A, B, C, (lambda: ops.gemm(A, B, C, m=m, n=n, k=k, lda=m, ldb=4096, ldc=n, a_kouter=True, b_kouter=True,
+                                      dtype=dt, out_dtype=torch.float32))
+
+
 def run(name, iters, lda_pad=0):
     m, n, k, ak, bk, nb, obf = SHAPES[name]
     dt = torch.bfloat16
+    if name == "wgrad_ih0_t":
+        A, B, C, f = run_step_t(name, iters)
+        return timed(name, f, iters, m, n, k, nb)
     if lda_pad < 0 and not ak:  # every A row the same 16 KiB-or-less row (lda 0): A from L2
         A = [torch.randn(1, k, device="cuda").to(dt) for _ in range(nb)]
     elif lda_pad and not ak:  # A rows lda_pad elements apart (a strided view)
@@ -49,6 +68,10 @@ def run(name, iters, lda_pad=0):
     bias = [torch.randn(n, device="cuda") for _ in range(nb)] if obf and not NO_BIAS else None
     f = lambda: ops.gemm(A, B, C, m=m, n=n, k=k, lda=m if ak else (0 if lda_pad < 0 else (lda_pad or k)), ldb=n if bk else k, ldc=n, a_kouter=bool(ak),
                          b_kouter=bool(bk), dtype=dt, out_dtype=odt, bias=bias)
+    return timed(name, f, iters, m, n, k, nb)
+
+
+def timed(name, f, iters, m, n, k, nb):
     f()
     torch.cuda.synchronize()
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

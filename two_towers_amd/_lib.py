@@ -125,9 +125,13 @@ _SIGS = {
     "tt_gemm": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(GemmBatch), c_int, c_long,
                         c_long, c_long, c_float, c_int, c_int, c_int, c_uint32, c_float, c_int, c_void_p,
                         c_void_p]),
+    "tt_gemm_ct": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(GemmBatch), c_int, c_long,
+                           c_long, c_long, c_float, c_int, c_int, c_int, c_uint32, c_float, c_int, c_void_p,
+                           c_int, c_void_p]),
     "tt_gemm_ws_size": (c_long, [c_int, c_int, c_int, c_int]),
     "tt_gemm_pick_splits": (c_int, [c_int, c_int, c_int, c_int]),
     "tt_gemm_bres_form": (c_int, [c_int, c_int, c_int, c_int, c_long, c_long]),
+    "tt_gemm_tall_form": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_long, c_long, c_int, c_int]),
     "tt_gru_fwd": (c_int, [c_int, POINTER(GruFwdRec), c_int, c_int, c_int, c_int, c_long, c_long, c_float,
                            c_void_p, c_long, c_void_p]),
     "tt_gru_bwd": (c_int, [c_int, POINTER(GruBwdRec), c_int, c_int, c_int, c_int, c_long, c_long, c_long,

@@ -49,6 +49,9 @@ enum Opt {
   OPT_HN_SCAN_V,        // h 256 hard-negative scan variant: 0 round-3 form, 4 64 queries per wave, 5 five-slot ring
   OPT_GEMM_W4,          // 1: bf16 NT GEMMs with bias on the four-wave 128x128-per-wave kernel (gemm_w4)
   OPT_BRES_FORM,        // B-resident short-K GEMM: 0 panel of B in LDS (gemm_bres), 1 weights in registers (gemm_wreg)
+  OPT_WGRAD_TALL,       // 1: bf16 TN products with 256 < M <= 320 (layer-0 dW_ih^T) on one 320-row tile per
+                        // column panel (gemm_tall) instead of a 256-row tile and a tail tile, a thin last
+                        // round as half tiles (2: whole tiles only, 3: half tiles only; 0: off)
   OPT_N
 };
 int opt(Opt o);

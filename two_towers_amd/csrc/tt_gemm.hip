@@ -44,7 +44,7 @@ constexpr OptDef kOpts[OPT_N] = {
     {"gru_fwd_xs", "TT_GRU_FWD_XS", 1},           {"hn_scan_gemm", "TT_HN_SCAN_GEMM", 0},
     {"gemm_iepi", "TT_GEMM_IEPI", 1},             {"bres_rows", "TT_BRES_ROWS", 32},
     {"hn_scan_v", "TT_HN_SCAN_V", 5},             {"gemm_w4", "TT_GEMM_W4", 0},
-    {"bres_form", "TT_BRES_FORM", 1},
+    {"bres_form", "TT_BRES_FORM", 1},             {"wgrad_tall", "TT_WGRAD_TALL", 1},
 };
 struct OptTable {
   std::atomic<int> v[OPT_N];
@@ -108,6 +108,7 @@ struct GemmArgs {
   int stream_out;   // write-through (sc1) output stores: big outputs
   int walk_g, walk_x;  // gemm_persist tile walk: column panels per group, workgroup sets (0: default)
   int nbatch;
+  int c_trans;  // splitk_reduce_kernel writes C transposed: C_b[n][m], ldc >= m (tt_gemm_ct)
   // gemm_persist<..., HN>: the hard-negative scan's epilogue (tt_score.hip): per (row, 64-column
   // chunk) only the maximum leaves, into cm[row * nch + chunk]; column label_off + row scores
   // -1 (the positive), columns >= N -inf
@@ -1302,7 +1303,180 @@ __global__ __launch_bounds__(512) void gemm_persist(GemmArgs g, int ntiles) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // trailing zero-page DMAs land before exit
 }
 
-// out_b[m][n] = alpha * sum_s part_b[s][m][n] (+ bias[n]) (+ out_b); V consecutive elements
+// ---- 320-row TN GEMM (option wgrad_tall; the layer-0 dW_ih^T = X0^T dG) ----------------
+// bf16 K-outer operands, fp32 out, 256 < M <= 320: gemm_kernel's 256-row tiles split such an
+// M into a full tile and a tail tile with at most 64 live rows that still pays a whole
+// tile's DMA and barrier schedule and fetches the B panel a second time. Here one workgroup
+// of 8 waves (2 x 4, 160 rows x 64 columns per wave: 10 x 4 accumulator fragments) owns all
+// of M and one 256-column panel of B; wave row wr takes rows 64 wr .. 64 wr + 63 of each wide
+// A sub-image and 32 wr .. 32 wr + 31 of the narrow one, so both wave rows run one code path.
+// The K loop runs 32-deep steps (one MFMA depth) through a ring of four 36 KiB LDS slots,
+// three steps of buffer LDS-DMAs in flight: per step A is two
+// [32 k][128 column] sub-images and one narrow [32 k][64 column] one (ttg::ko16n_off), B two
+// [32 k][128 column] sub-images, 36 wave-instructions of 1 KiB dealt round-robin over the
+// waves (waves 0-3 issue five, waves 4-7 four; each wave counts its own). K-rows past the
+// split's end read zero through num_records, so every step issues all its DMAs and the
+// counted waits are exact. Columns of A past M and of B past N hold whatever lies there and
+// only reach accumulator rows / columns that are never stored. The A fragments of a step
+// are read in two groups of five. Transposed accumulate (B fragment first, as Loop8 CT):
+// every lane holds four consecutive output columns, stored from registers. Same MFMA, same
+// ascending 32-deep k steps from the split's first K-tile, same split boundaries
+// (kt_per_split 64-deep K-tiles) as gemm_kernel: bit-identical to it at equal splits.
+// The split count stays the one gemm_kernel's grid gets, so the sums do not move; where the
+// units (problem, slice, panel) then leave a last round at most half full, those units run
+// as two workgroups each (HALF): half hf takes columns 64 hf .. 64 hf + 63 of each wide A
+// sub-image and 32 hf .. 32 hf + 31 of the narrow one (160 rows; wave row wr half of that:
+// 5 x 4 accumulator fragments per wave), with the whole A image staged as in a full tile.
+// The two halves are adjacent ids, so the unit's B panel comes from L2 for the second.
+namespace tall {
+constexpr int AW = 8192, AN = 4096;  // bytes of a wide / the narrow sub-image of one step
+constexpr int BOFF = 2 * AW + AN;    // B's sub-images follow A's
+constexpr int SLOT = BOFF + 2 * AW;  // 36 KiB
+constexpr int NS = 4;                // ring slots
+constexpr int NDMA = SLOT / 1024;    // wave-instructions per step
+constexpr int KS = 32;               // k-rows per step
+}  // namespace tall
+
+template <bool HALF>
+__global__ __launch_bounds__(512) void gemm_tall(GemmArgs g, int u0) {
+  using namespace tall;
+  constexpr int NA = HALF ? 5 : 10;  // 16-row accumulator blocks per wave
+  __shared__ __attribute__((aligned(16))) char lds[NS * SLOT];
+  // ids enumerate (batch entry * split, column panel), the panel fastest: the panels of one
+  // problem and K-slice share A in an XCD's L2
+  const int ntn = (g.N + 255) / 256;
+  const int id = xcd_remap(blockIdx.x, gridDim.x);
+  const int hf = HALF ? id & 1 : 0;             // which half of the unit's rows
+  const int u = u0 + (HALF ? id >> 1 : id);     // this launch's units start at u0
+  const int bs = u / ntn, nt = u - bs * ntn;
+  const int bi = bs / g.splits, s = bs - bi * g.splits;
+  const int n0 = nt * 256;
+  const bf16_t* A = static_cast<const bf16_t*>(g.a[bi]);
+  const bf16_t* B = static_cast<const bf16_t*>(g.b[bi]);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int wr = wave >> 2, wn = (wave & 3) * 64;
+  // accumulator block a of the wave: blocks a % 5 < 4 lie in a wide A sub-image, a % 5 == 4 in
+  // the narrow one; a_col is the block's first column there
+  auto a_sub = [&](int a) { return HALF ? a >> 1 : a / 5; };
+  auto a_col = [&](int a) {
+    if (HALF) return a == 4 ? 32 * hf + 16 * wr : 64 * hf + 32 * wr + 16 * (a & 1);
+    return a % 5 == 4 ? 32 * wr + 16 * (a / 5) : 64 * wr + 16 * (a % 5);
+  };
+
+  f32x4 acc[NA][4];
+#pragma unroll
+  for (int i = 0; i < NA; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int nk = (g.K * 2 + ttg::KTB - 1) / ttg::KTB;
+  const int kt0 = s * g.kt_per_split;
+  const int kt1 = min(nk, kt0 + g.kt_per_split);
+  if (kt0 < kt1) {
+    const int nst = 2 * (kt1 - kt0);
+    const long k0 = (long)kt0 * 64;
+    const long krows = min((long)g.K, (long)kt1 * 64) - k0;  // k-rows of this split: the rest read zero
+    const ttg::tt_rsrc4 ra = ttg::make_rsrc4(A + k0 * g.lda, (uint32_t)(((krows - 1) * g.lda + g.M) * 2));
+    const ttg::tt_rsrc4 rb = ttg::make_rsrc4(B + k0 * g.ldb, (uint32_t)(((krows - 1) * g.ldb + g.N) * 2));
+    const uint32_t da = (uint32_t)(KS * g.lda * 2), db = (uint32_t)(KS * g.ldb * 2);  // bytes per step
+    // this wave's DMAs of a step: wave-instructions j = wave + 8 t < 36; 0-15 A wide, 16-19 A
+    // narrow, 20-35 B, the slot's images in that order (instruction j writes KiB j of the slot)
+    uint32_t voff[5];
+#pragma unroll
+    for (int t = 0; t < 5; ++t) {
+      const int j = wave + 8 * t;
+      long e;
+      if (j < 16) {
+        const int p = (j & 7) * 64 + lane, kl = p >> 4, c = (p & 15) ^ (ttg::ko_v(kl) << 1);
+        e = (long)kl * g.lda + (j >> 3) * 128 + c * 8;
+      } else if (j < 20) {
+        const int p = (j - 16) * 64 + lane, kl = p >> 3, c = (p & 7) ^ (ttg::kon_v(kl) << 1);
+        e = (long)kl * g.lda + 256 + c * 8;
+      } else {
+        const int b = j - 20, p = (b & 7) * 64 + lane, kl = p >> 4, c = (p & 15) ^ (ttg::ko_v(kl) << 1);
+        e = (long)kl * g.ldb + n0 + (b >> 3) * 128 + c * 8;
+      }
+      voff[t] = (uint32_t)(e * 2);
+    }
+    const uint32_t base = __builtin_amdgcn_readfirstlane(ttg::lds_addr_of(lds));
+    // t = 0, 1 are A's wide pieces and t = 3, 4 B's on every wave; t = 2 is A's narrow piece
+    // on waves 0-3 and a piece of B on waves 4-7
+    const bool a2 = wave < 4;
+    ttg::tt_rsrc4 r2;
+    r2.x = a2 ? ra.x : rb.x;
+    r2.y = a2 ? ra.y : rb.y;
+    r2.z = a2 ? ra.z : rb.z;
+    r2.w = ra.w;
+    const uint32_t d2 = a2 ? da : db;
+    auto issue = [&](int st) {
+      const uint32_t sl = base + (uint32_t)(st & (NS - 1)) * SLOT + (uint32_t)wave * 1024u;
+      // the step's byte advance goes into the per-lane offset, the part of the address that
+      // the range check against num_records is documented to cover
+      const uint32_t sa = (uint32_t)st * da, sb = (uint32_t)st * db;
+      ttg::dma16_buf(ra, voff[0] + sa, 0u, sl);
+      ttg::dma16_buf(ra, voff[1] + sa, 0u, sl + 8 * 1024u);
+      ttg::dma16_buf(r2, voff[2] + (uint32_t)st * d2, 0u, sl + 16 * 1024u);
+      ttg::dma16_buf(rb, voff[3] + sb, 0u, sl + 24 * 1024u);
+      if (a2) ttg::dma16_buf(rb, voff[4] + sb, 0u, sl + 32 * 1024u);
+    };
+    // one step's MFMAs, the A fragments in groups of five blocks
+    auto step = [&](const char* sl) {
+      uint4 fb[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) fb[j] = ttg::frag<bf16_t, true>(sl + BOFF + (wn >> 7) * AW, (wn & 127) + 16 * j, 0);
+#pragma unroll
+      for (int h = 0; h < NA / 5; ++h) {
+        uint4 fa[5];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) fa[i] = ttg::frag<bf16_t, true>(sl + a_sub(5 * h + i) * AW, a_col(5 * h + i), 0);
+        fa[4] = ttg::frag_ko16n(sl + 2 * AW, a_col(5 * h + 4));
+#pragma unroll
+        for (int i = 0; i < 5; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[5 * h + i][j] = ttg::mma<bf16_t>(fb[j], fa[i], acc[5 * h + i][j]);
+        __builtin_amdgcn_sched_barrier(0);  // one group per scheduling region (registers)
+      }
+    };
+    issue(0);
+    issue(1);
+    issue(2);
+    for (int st = 0; st < nst; ++st) {
+      // steps st + 1 and st + 2 may stay in flight: this wave's DMAs of step st have landed
+      if (wave < 4) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      __builtin_amdgcn_s_barrier();  // ... and every wave's; the slot of step st - 1 is free
+      issue(st + 3);
+      const char* sl = lds + (st & (NS - 1)) * SLOT;
+      step(sl);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing (all-zero) DMAs land before exit
+  }
+
+  // epilogue: acc[a][j][e] = C(row, n0 + wn + 16 j + 4 (lane >> 4) + e), row = the block's
+  // image column (+ 128 per wide sub-image, 256 for the narrow one) + (lane & 15)
+  const bool partial = g.splits > 1;
+  float* C = partial ? static_cast<float*>(g.c[bi]) + (long)s * g.part_stride : static_cast<float*>(g.c[bi]);
+  const long ldc = partial ? (long)g.N : g.ldc;
+  const int q = lane >> 4, lr = lane & 15;
+#pragma unroll
+  for (int i = 0; i < NA; ++i) {
+    const int gm = (i % 5 < 4 ? 128 * a_sub(i) : 256) + a_col(i) + lr;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = n0 + wn + 16 * j + 4 * q;
+      if (gm >= g.M || c >= g.N) continue;
+      float v[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = partial ? acc[i][j][e] : acc[i][j][e] * g.alpha + 0.f;
+      float* dst = C + (long)gm * ldc + c;
+      if (c + 4 <= g.N && g.vec_ok) *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+      else
+        for (int e = 0; e < 4 && c + e < g.N; ++e) dst[e] = v[e];
+    }
+  }
+}
+
+// out_b[m][n] (c_trans: out_b[n][m]) = alpha * sum_s part_b[s][m][n] (+ bias[n]) (+ out_b); V consecutive elements
 // of one row per thread (V 4: N % 4 == 0, 16-byte partial loads), the slices summed in order
 // s = 0, 1, ... either way
 template <typename TO, int V>
@@ -1334,7 +1508,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* ws, lon
     for (int u = 0; u < V; ++u) {
       float x = v[u] * g.alpha;
       if (bias) x += bias[n0 + u];
-      TO* p = C + (long)m * g.ldc + n0 + u;
+      TO* p = g.c_trans ? C + (long)(n0 + u) * g.ldc + m : C + (long)m * g.ldc + n0 + u;
       if (g.beta) x += Elt<TO>::ld(p);
       Elt<TO>::st(p, x);
     }
@@ -1684,12 +1858,47 @@ bool try_bres(int akout, int bkout, bool shift, const GemmArgs& g, int nbatch, h
   }
 }
 
+// Whether a product runs on gemm_tall (option wgrad_tall): bf16 K-outer operands, fp32 out,
+// nothing but alpha in the epilogue, 256 < M <= 320 in whole 16-byte chunks (N too), and
+// every split's k-rows, three steps of prefetch past its end included, within a 32-bit byte
+// offset of the split's first row.
+bool tall_form_for(bool bf16_in, bool f32_out, int akout, int bkout, bool plain, int M, int N, long lda, long ldb,
+                   int kt_per_split) {
+  if (tt::opt(tt::OPT_WGRAD_TALL) == 0 || !bf16_in || !f32_out || !akout || !bkout || !plain) return false;
+  if (M <= 256 || M > 320 || M % 8 || N % 8 || N <= 0) return false;
+  if (tt::opt(tt::OPT_GEMM_REGSTAGE) != 0) return false;
+  const long span = ((long)kt_per_split * 64 + 4 * tall::KS) * 2;
+  return span * lda < (1L << 32) && span * ldb < (1L << 32);
+}
+bool gemm_args_plain(const GemmArgs& g, bool shift, int nbatch) {
+  if (shift || g.a_split > 0 || g.beta || g.relu || g.drop_thresh) return false;
+  for (int b = 0; b < nbatch; ++b)
+    if (g.bias[b]) return false;
+  return true;
+}
+
 template <typename T, typename TO>
 int launch_gemm(int akout, int bkout, bool shift, GemmArgs& g, int nbatch, hipStream_t st) {
   constexpr int EPC = 16 / (int)sizeof(T);
   {
     int rc = 0;
     if (try_bres<T, TO>(akout, bkout, shift, g, nbatch, st, &rc)) return rc;
+  }
+  if (tall_form_for(std::is_same<T, bf16_t>::value, std::is_same<TO, float>::value, akout, bkout,
+                    gemm_args_plain(g, shift, nbatch), g.M, g.N, g.lda, g.ldb, g.kt_per_split)) {
+    // units (problem, slice, panel): whole tiles, except that a last round over the 256 CUs
+    // that would be at most half full runs as half tiles, two workgroups per unit (option
+    // wgrad_tall 2: whole tiles only, 3: half tiles only)
+    const long units = (long)tt_ceil_div(g.N, 256) * nbatch * g.splits;
+    const int mode = tt::opt(tt::OPT_WGRAD_TALL);
+    long nfull = units;
+    if (mode == 3) nfull = 0;
+    else if (mode != 2 && units % 256 > 0 && units % 256 <= 128) nfull = units - units % 256;
+    if (nfull > 0) hipLaunchKernelGGL(gemm_tall<false>, dim3((unsigned)nfull), dim3(512), 0, st, g, 0);
+    if (units > nfull)
+      hipLaunchKernelGGL(gemm_tall<true>, dim3((unsigned)(2 * (units - nfull))), dim3(512), 0, st, g, (int)nfull);
+    TT_CHECK_LAUNCH("gemm_tall");
+    return 0;
   }
   const bool dma = (akout ? g.M % EPC == 0 : g.K % EPC == 0) && (bkout ? g.N % EPC == 0 : g.K % EPC == 0) &&
                    g.force_regstage != 1;
@@ -1789,6 +1998,24 @@ extern "C" int tt_gemm_bres_form(int m, int n, int k, int nbatch, long lda, long
   return bres_form_for(m, n, k, nbatch, lda, ldc);
 }
 
+// K-tiles (128 bytes of K) per split and the split count tt_gemm really uses
+static void split_plan(int k, int esz, int* splits, int* kt_per_split) {
+  const int nk = tt_ceil_div((long)k * esz, 128);
+  int s = *splits < 1 ? 1 : *splits;
+  if (s > nk) s = nk > 0 ? nk : 1;
+  *kt_per_split = nk > 0 ? tt_ceil_div(nk, s) : 1;
+  *splits = nk > 0 ? tt_ceil_div(nk, *kt_per_split) : 1;
+}
+
+extern "C" int tt_gemm_tall_form(int dtype, int out_dtype, int a_kouter, int b_kouter, int m, int n, int k, long lda,
+                                 long ldb, int splits, int extras) {
+  int ktps = 1;
+  split_plan(k, dtype == TT_DT_BF16 ? 2 : 4, &splits, &ktps);
+  return tall_form_for(dtype == TT_DT_BF16, out_dtype == TT_DT_F32, a_kouter, b_kouter, extras == 0, m, n, lda, ldb, ktps)
+             ? 1
+             : 0;
+}
+
 extern "C" long tt_gemm_ws_size(int m, int n, int nbatch, int splits) {
   (void)m;
   return splits > 1 ? (long)m * n * nbatch * splits : 0;
@@ -1818,6 +2045,14 @@ extern "C" int tt_gemm(int dtype, int out_dtype, int a_kouter, int b_kouter, int
                        const tt_gemm_batch* batch, int nbatch, long lda, long ldb, long ldc,
                        float alpha, int beta_accum, int relu, int seq_t, uint32_t drop_seed,
                        float drop_p, int splits, float* splitk_ws, void* stream) {
+  return tt_gemm_ct(dtype, out_dtype, a_kouter, b_kouter, m, n, k, batch, nbatch, lda, ldb, ldc, alpha, beta_accum, relu,
+                    seq_t, drop_seed, drop_p, splits, splitk_ws, 0, stream);
+}
+
+extern "C" int tt_gemm_ct(int dtype, int out_dtype, int a_kouter, int b_kouter, int m, int n, int k,
+                          const tt_gemm_batch* batch, int nbatch, long lda, long ldb, long ldc,
+                          float alpha, int beta_accum, int relu, int seq_t, uint32_t drop_seed,
+                          float drop_p, int splits, float* splitk_ws, int c_trans, void* stream) {
   TT_CHECK_ARG(dtype == TT_DT_F32 || dtype == TT_DT_BF16, "tt_gemm: bad dtype %d", dtype);
   TT_CHECK_ARG(out_dtype == TT_DT_F32 || out_dtype == dtype, "tt_gemm: bad out_dtype %d", out_dtype);
   TT_CHECK_ARG(nbatch >= 1 && nbatch <= 4, "tt_gemm: nbatch %d not in [1,4]", nbatch);
@@ -1862,11 +2097,10 @@ extern "C" int tt_gemm(int dtype, int out_dtype, int a_kouter, int b_kouter, int
   g.drop_row0 = batch->drop_row0;
   g.drop_thresh = drop_p > 0.f ? (uint32_t)(drop_p * 16777216.0f + 0.5f) : 0u;
   g.drop_inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
-  const int nk = tt_ceil_div((long)k * esz, 128);
-  if (splits > nk) splits = nk > 0 ? nk : 1;
-  g.kt_per_split = nk > 0 ? tt_ceil_div(nk, splits) : 1;
-  splits = nk > 0 ? tt_ceil_div(nk, g.kt_per_split) : 1;
+  split_plan(k, esz, &splits, &g.kt_per_split);
   g.splits = splits;
+  TT_CHECK_ARG(!c_trans || splits > 1, "tt_gemm_ct: a transposed C needs split-K (splits %d)", splits);
+  g.c_trans = c_trans != 0;
   {
     const int osz = out_dtype == TT_DT_BF16 ? 2 : 4;
     bool ok = (ldc * osz) % 16 == 0;

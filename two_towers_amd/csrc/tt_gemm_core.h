@@ -43,6 +43,11 @@ TT_DEV int kc_off(int row, int c) { return row * KTB + ((c ^ ((row >> 1) & 7)) <
 // KO bf16 image: k-rows of 256 B (128 columns), 16-B chunk c stored at c ^ 2v(k).
 TT_DEV int ko_v(int k) { return (k & 3) | (((k >> 3) & 1) << 2); }
 TT_DEV int ko16_off(int k, int c) { return k * 256 + ((c ^ (ko_v(k) << 1)) << 4); }
+// Narrow KO bf16 image: k-rows of 128 B (64 columns), 16-B chunk c stored at c ^ 2w(k). Two
+// consecutive k-rows share a 256-B bank window, so k's bit 0 already separates them and the
+// XOR takes the other two k bits a fragment read spans.
+TT_DEV int kon_v(int k) { return ((k >> 1) & 1) | (((k >> 3) & 1) << 1); }
+TT_DEV int ko16n_off(int k, int c) { return k * 128 + ((c ^ (kon_v(k) << 1)) << 4); }
 // KO fp32 image: k-rows of 512 B (128 columns), column m stored at m ^ 16*((k>>2)&1).
 TT_DEV int ko32_off_chunk(int k, int c) { return k * 512 + ((c ^ (((k >> 2) & 1) << 2)) << 4); }
 TT_DEV int ko32_off_elem(int k, int m) { return k * 512 + ((m ^ (((k >> 2) & 1) << 4)) << 2); }
@@ -156,6 +161,25 @@ TT_DEV uint4 frag(const char* img, int r0, int ks) {
     v.w = *reinterpret_cast<const uint32_t*>(img + ko32_off_elem(kb + 3, m));
     return v;
   }
+}
+
+// The bf16 K-outer fragment of frag<T, true> (sub-step 0) from a narrow image (ko16n_off):
+// 16 columns starting at image column r0 < 64, k = 0..31.
+TT_DEV uint4 frag_ko16n(const char* img, int r0) {
+  const int lane = threadIdx.x & 63;
+  const int g = lane >> 4, i4 = lane & 15, q = i4 >> 2, p = i4 & 3;
+  const int k0 = 8 * g + q;
+  const int cc = (r0 >> 2) + p;  // 8-byte chunk along the row
+  const int o0 = ko16n_off(k0, cc >> 1) + ((cc & 1) << 3);
+  const int o1 = ko16n_off(k0 + 4, cc >> 1) + ((cc & 1) << 3);
+  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + o0));
+  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + o1));
+  uint4 v;
+  v.x = (uint32_t)(uint16_t)lo[0] | ((uint32_t)(uint16_t)lo[1] << 16);
+  v.y = (uint32_t)(uint16_t)lo[2] | ((uint32_t)(uint16_t)lo[3] << 16);
+  v.z = (uint32_t)(uint16_t)hi[0] | ((uint32_t)(uint16_t)hi[1] << 16);
+  v.w = (uint32_t)(uint16_t)hi[2] | ((uint32_t)(uint16_t)hi[3] << 16);
+  return v;
 }
 
 template <typename T>

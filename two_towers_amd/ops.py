@@ -33,9 +33,12 @@ def gemm(a: Sequence[torch.Tensor], b: Sequence[torch.Tensor], c: Sequence[torch
          out_dtype: torch.dtype, bias: Sequence[torch.Tensor | None] | None = None,
          bshift: Sequence[int] | None = None, alpha: float = 1.0, accumulate: bool = False,
          relu: bool = False, seq_t: int = 0, drop_seed: int = 0, drop_p: float = 0.0, drop_row0: int = 0,
-         splits: int | None = None, a_hi: Sequence[torch.Tensor] | None = None, a_split: int = 0):
+         splits: int | None = None, a_hi: Sequence[torch.Tensor] | None = None, a_split: int = 0,
+         c_trans: bool = False):
     """Batched C_i = alpha * op(A_i) op(B_i)^T (+bias) for up to 4 problems of one shape.
-    With a_kouter and a_split > 0, A columns >= a_split are read from a_hi[i]."""
+    With a_kouter and a_split > 0, A columns >= a_split are read from a_hi[i].
+    c_trans: C_i is stored [n][m] (ldc >= m), written by the split-K reduction (tt_gemm_ct):
+    the call must split K (see gemm_splits)."""
     nb = len(a)
     assert 1 <= nb <= 4 and len(b) == nb and len(c) == nb
     bt = GemmBatch()
@@ -53,15 +56,26 @@ def gemm(a: Sequence[torch.Tensor], b: Sequence[torch.Tensor], c: Sequence[torch
     bt.drop_row0 = drop_row0 & 0xFFFFFFFF
     lib = _lib.load()
     if splits is None:
-        splits = lib.tt_gemm_pick_splits(m, n, k, nb)
+        splits = gemm_splits(m, n, k, nb, dtype)
     ws = None
     if splits > 1 and not relu and drop_p == 0.0:
         ws = torch.empty(lib.tt_gemm_ws_size(m, n, nb, splits), dtype=torch.float32, device=c[0].device)
     else:
         splits = 1
-    call("tt_gemm", dtype_code(dtype), dtype_code(out_dtype), int(a_kouter), int(b_kouter), m, n, k,
+    call("tt_gemm_ct", dtype_code(dtype), dtype_code(out_dtype), int(a_kouter), int(b_kouter), m, n, k,
          ctypes.byref(bt), nb, lda, ldb, ldc, alpha, int(accumulate), int(relu), seq_t, drop_seed & 0xFFFFFFFF,
-         drop_p, splits, ptr(ws), stream_ptr(c[0].device))
+         drop_p, splits, ptr(ws), int(c_trans), stream_ptr(c[0].device))
+
+
+def gemm_splits(m: int, n: int, k: int, nb: int, dtype: torch.dtype) -> int:
+    """The split count gemm() uses when none is given, after tt_gemm's clamping to one
+    K-tile (128 bytes of K) per split at least."""
+    s = _lib.load().tt_gemm_pick_splits(m, n, k, nb)
+    nk = (k * _esz(dtype) + 127) // 128
+    if nk <= 0:
+        return 1
+    per = (nk + min(max(s, 1), nk) - 1) // min(max(s, 1), nk)
+    return (nk + per - 1) // per
 
 
 def embed_gather(table: torch.Tensor, ids: torch.Tensor, out: torch.Tensor):

@@ -543,15 +543,20 @@ def _weight_grads(cfg, B, T, dG, Xin, K, ldx, Y, kr=None):
     with timing.region("wgrad_ih", 1, 2.0 * 3 * H * kr * BT * 2 * n,
                        float(n * (esz * BT * (6 * H + kr) + 2 * 3 * H * kr * 4))):
         if _WGRAD_T and dt == torch.bfloat16 and 0 < K % 256 <= 128:
-            # layer 0 (K = Ep 320): dW_ih^T = Xin^T dG puts the padded width on M, where the
-            # tail tile's second wave row lies wholly past M and skips its MFMAs (the
-            # 256x256 loop, tt_gemm_core.h Loop8::quad): 1.5 tiles of work per 256 gate
-            # rows instead of 2 for the N tail
-            cT = [_alloc((K, 3 * H), torch.float32, dev) for _ in c_ih]
-            ops.gemm(b_ih, a_ih, cT, m=K, n=3 * H, k=BT, lda=ldx, ldb=8 * H, ldc=3 * H, a_kouter=True,
-                     b_kouter=True, dtype=dt, out_dtype=torch.float32)
-            for c, ct in zip(c_ih, cT):
-                c.copy_(ct.t())
+            # layer 0 (K = Ep 320): dW_ih^T = Xin^T dG puts the padded width on M, where one
+            # 320-row tile per dG panel covers it (tt_gemm.hip gemm_tall, option wgrad_tall;
+            # with the option off, a 256-row tile and a tail tile whose second wave row
+            # skips its MFMAs, tt_gemm_core.h Loop8::quad)
+            if ops.gemm_splits(K, 3 * H, BT, len(c_ih), dt) > 1:
+                # the split-K reduction writes [3H, K] itself (same sums, no transposed copy)
+                ops.gemm(b_ih, a_ih, c_ih, m=K, n=3 * H, k=BT, lda=ldx, ldb=8 * H, ldc=K, a_kouter=True,
+                         b_kouter=True, dtype=dt, out_dtype=torch.float32, c_trans=True)
+            else:
+                cT = [_alloc((K, 3 * H), torch.float32, dev) for _ in c_ih]
+                ops.gemm(b_ih, a_ih, cT, m=K, n=3 * H, k=BT, lda=ldx, ldb=8 * H, ldc=3 * H, a_kouter=True,
+                         b_kouter=True, dtype=dt, out_dtype=torch.float32)
+                for c, ct in zip(c_ih, cT):
+                    c.copy_(ct.t())
         else:
             ops.gemm(a_ih, b_ih, c_ih, m=3 * H, n=K, k=BT, lda=8 * H, ldb=ldx, ldc=K, a_kouter=True,
                      b_kouter=True, dtype=dt, out_dtype=torch.float32)

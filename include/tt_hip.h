@@ -348,25 +348,51 @@ long tt_infonce_bwd_ws_size(int dtype, long bq, long nd, int h);
 /* Hard-negative mining, batched over rows (get_hard_negatives,
  * enhanced_two_tower.py:123-133): sims = qn dn^T (cosine for normalised inputs), the
  * positive column label_offset+i set to -1 (label_offset < 0: no column masked), top-k
- * (1 <= k <= min(16, nd)) indices per row sorted by descending similarity; ties broken
- * towards the lower column index. Also the scoring step of the serving /search
+ * (1 <= k <= min(tt_topk_max(), nd)) indices per row sorted by descending similarity; ties
+ * broken towards the lower column index. Also the scoring step of the serving /search
  * (server/python-api/app.py:94-101, label_offset < 0).
  * idx [bq, k] int32, val [bq, k] fp32 (optional). ws: tt_hardneg_ws_size bytes.
- * bf16 with h in {128, 256} (qn, dn 16-byte aligned, else TT_EINVAL) never stores the score matrix
- * (streamed MFMA scan + exact chunk selection + bit-identical rescoring, tt_score.hip). */
+ * k <= 16: bf16 with h in {128, 256, 512} (qn, dn 16-byte aligned, else TT_EINVAL) never stores the
+ * score matrix (streamed MFMA scan + exact chunk selection + bit-identical rescoring,
+ * tt_score.hip); other shapes store it (tt_gemm) and take a column-split top-k.
+ * k > 16: every shape stores the score block (bq * nd * 4 bytes of ws) through tt_gemm and
+ * selects with tt_topk_rows. bf16 scores are the same MFMA sums on every path, so a
+ * k <= 16 answer is a prefix of a larger-k answer, bit for bit. */
 int tt_hardneg_topk(int dtype, const void* qn, long bq, const void* dn, long nd, int h,
                     long label_offset, int k, int32_t* idx, float* val, void* ws, void* stream);
 long tt_hardneg_ws_size(int dtype, long bq, long nd, int h, int k);
 
 /* Serving search (server/python-api/app.py:94-101: F.cosine_similarity of one encoded
  * query against every cached document row, then torch.topk): qn [Q, h] fp32 normalised
- * queries, dn [N, h] dtype normalised documents (resident), top-k (1 <= k <= min(16, N))
- * indices/scores per query, value descending, ties towards the lower document index.
- * Q <= 64: one fused pass over dn per 8 queries (per-lane top-k, no score matrix);
- * larger Q: cosine GEMM + column-split top-k. h % 8 == 0. ws: tt_search_ws_size bytes. */
+ * queries, dn [N, h] dtype normalised documents (resident), top-k
+ * (1 <= k <= min(tt_topk_max(), N)) indices/scores per query, value descending, ties towards
+ * the lower document index. h % 8 == 0. ws: tt_search_ws_size bytes.
+ * k <= 16, Q <= 64: one fused pass over dn per 8 queries (per-lane top-k, no score matrix);
+ * k <= 16, larger Q: cosine GEMM + column-split top-k.
+ * k > 16, any Q: cosine GEMM into the workspace (Q * N * 4 bytes of it), then tt_topk_rows.
+ * The scores are then the GEMM's (MFMA sums); the fused scan's are VALU fma chains and can
+ * differ from them in the last bit. A k <= 16 answer is therefore guaranteed to be a
+ * prefix of a larger-k answer only where both use the GEMM: Q > 64. */
 int tt_search_topk(int dtype, const float* qn, long Q, const void* dn, long N, int h, int k,
                    int32_t* idx, float* val, void* ws, void* stream);
 long tt_search_ws_size(int dtype, long Q, long N, int h, int k);
+
+/* Largest k of tt_topk_rows, tt_search_topk and tt_hardneg_topk: 1024. */
+int tt_topk_max(void);
+/* Exact top-k of every row of a dense fp32 block S [rows, cols] (leading dimension ld):
+ * idx [rows, k] int32 and val [rows, k] fp32 (optional), 1 <= k <= min(1024, cols), ordered
+ * by value descending, ties towards the lower column. Column label_offset + row reads as
+ * -1 (label_offset < 0: none) and is returned with that value once k reaches it
+ * (enhanced_two_tower.py:130-132). -0.0 and +0.0 are equal and tie by column; infinities
+ * and denormals order as floats; val holds the stored values; NaN inputs are unspecified.
+ * Radix select of the k-th largest key per (row, column chunk) in LDS, ordered compaction,
+ * bitonic sort of the selected; long rows in levels (tt_select.hip). Deterministic: no
+ * float atomics, and nothing depends on the previous contents of ws
+ * (tt_topk_rows_ws_size(rows, cols, k) bytes; 0 for rows of at most 8192 columns).
+ * rows = 0 is a no-op. */
+int tt_topk_rows(const float* S, long rows, long cols, long ld, long label_offset, int k,
+                 int32_t* idx, float* val, void* ws, void* stream);
+long tt_topk_rows_ws_size(long rows, long cols, int k);
 
 /* MarginRankingLoss with explicit negatives (enhanced_two_tower.py:102-121) on
  * normalised vectors: pos_i = qn_i.dn_{label_offset+i}, negm_i = mean_j qn_i.dn_{idx[i,j]},

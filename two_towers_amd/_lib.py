@@ -166,6 +166,10 @@ _SIGS = {
     "tt_search_topk": (c_int, [c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p,
                                c_void_p, c_void_p]),
     "tt_search_ws_size": (c_long, [c_int, c_long, c_long, c_int, c_int]),
+    "tt_topk_max": (c_int, []),
+    "tt_topk_rows": (c_int, [c_void_p, c_long, c_long, c_long, c_long, c_int, c_void_p, c_void_p, c_void_p,
+                             c_void_p]),
+    "tt_topk_rows_ws_size": (c_long, [c_long, c_long, c_int]),
     "tt_margin_fwd": (c_int, [c_void_p, c_long, c_void_p, c_long, c_int, c_long, c_void_p, c_int, c_float,
                               c_void_p, c_void_p]),
     "tt_margin_bwd": (c_int, [c_void_p, c_long, c_void_p, c_long, c_int, c_long, c_void_p, c_int, c_float,
@@ -212,6 +216,17 @@ def check(rc: int, what: str = ""):
 def call(name: str, *args):
     lib = load()
     check(getattr(lib, name)(*args), name)
+
+
+_topk_max: int | None = None
+
+
+def topk_max() -> int:
+    """Largest k of tt_topk_rows / tt_search_topk / tt_hardneg_topk (tt_topk_max)."""
+    global _topk_max
+    if _topk_max is None:
+        _topk_max = int(load().tt_topk_max())
+    return _topk_max
 
 
 def get_option(name: str) -> int:

@@ -833,6 +833,7 @@ int tt_hn_scan_topk(const void* qn, long bq, const void* dn, long nd, int h, lon
                     float* val, void* ws, void* stream);
 
 extern "C" long tt_hardneg_ws_size(int dtype, long bq, long nd, int h, int k) {
+  if (k > TOPK_MAX) return ((bq * nd * 4 + 255) & ~255L) + tt_topk_rows_ws_size(bq, nd, k);
   if (tt_hn_scan_supported(dtype, h)) return tt_hn_scan_ws_size(bq, nd, k < 1 ? 1 : k);
   const long ncand = tt_ceil_div(nd, ttk::split_chunk(bq, nd)) * (long)TOPK_MAX;
   return ((bq * nd * 4 + 255) & ~255L) + 2 * ((bq * ncand * 4 + 255) & ~255L);
@@ -840,9 +841,19 @@ extern "C" long tt_hardneg_ws_size(int dtype, long bq, long nd, int h, int k) {
 
 extern "C" int tt_hardneg_topk(int dtype, const void* qn, long bq, const void* dn, long nd, int h, long label_offset,
                                int k, int32_t* idx, float* val, void* ws, void* stream) {
-  TT_CHECK_ARG(k >= 1 && k <= TOPK_MAX && k <= nd, "tt_hardneg_topk: k=%d (nd=%ld)", k, nd);
+  TT_CHECK_ARG(k >= 1 && k <= ttk::SEL_MAX && k <= nd, "tt_hardneg_topk: k=%d needs 1 <= k <= min(%d, nd=%ld)", k,
+               ttk::SEL_MAX, nd);
   TT_CHECK_ARG(label_offset < 0 || label_offset + bq <= nd, "tt_hardneg_topk: labels outside [0, nd)");
   if (bq == 0) return 0;
+  if (k > TOPK_MAX) {  // every shape: the score block, then the radix selection (tt_select.hip)
+    float* S = static_cast<float*>(ws);
+    tt_gemm_batch g{};
+    g.a[0] = qn; g.b[0] = dn; g.c[0] = S;
+    TT_PROPAGATE(tt_gemm(dtype, TT_DT_F32, 0, 0, (int)bq, (int)nd, h, &g, 1, h, h, nd, 1.f, 0, 0, 0, 0, 0.f, 1,
+                         nullptr, stream));
+    return tt_topk_rows(S, bq, nd, nd, label_offset, k, idx, val,
+                        static_cast<char*>(ws) + ((bq * nd * 4 + 255) & ~255L), stream);
+  }
   if (tt_hn_scan_supported(dtype, h)) {
     TT_CHECK_ARG((((uintptr_t)qn | (uintptr_t)dn) & 15) == 0, "tt_hardneg_topk: bf16 rows must be 16-byte aligned");
     return tt_hn_scan_topk(qn, bq, dn, nd, h, label_offset, k, idx, val, ws, stream);

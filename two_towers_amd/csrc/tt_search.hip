@@ -10,6 +10,7 @@
 //   larger Q: cosine GEMM into a score block, then ttk::topk_split_kernel (many waves
 //     per row, one column chunk each) and the same merge: the long rows of a large
 //     document pool are scanned by many waves instead of one.
+//   k > 16 (any Q): the same cosine GEMM, then tt_topk_rows (tt_select.hip).
 // Ordering everywhere: value descending, ties towards the lower document index.
 #include <cfloat>
 #include <climits>
@@ -77,13 +78,21 @@ __global__ __launch_bounds__(256) void search_scan_kernel(const float* __restric
 }
 
 struct SearchWs {
-  long cv, ci, qd, S, total;
+  long cv, ci, qd, S, sel, total;
 };
 
 inline SearchWs search_ws(int dtype, long Q, long N, int h, int k) {
   auto al = [](long x) { return (x + 255) & ~255L; };
   SearchWs w{};
   long ncand, off = 0;
+  if (k > SK_MAX) {  // every Q: queries in the scoring dtype, the score block, the selection's lists
+    const int esz = dtype == TT_DT_BF16 ? 2 : 4;
+    w.qd = off; off = al(off + Q * h * esz);
+    w.S = off;  off = al(off + Q * N * 4);
+    w.sel = off;
+    w.total = off + tt_topk_rows_ws_size(Q, N, k);
+    return w;
+  }
   if (Q <= SCAN_QMAX) {
     ncand = tt_ceil_div(N, BLK_DOCS) * 4 * k;
     w.qd = w.S = 0;
@@ -99,6 +108,18 @@ inline SearchWs search_ws(int dtype, long Q, long N, int h, int k) {
   }
   w.total = off;
   return w;
+}
+
+// qn in the scoring dtype at ws + w.qd, then S = qd dn^T at ws + w.S (the cosine GEMM)
+int search_scores(int dtype, const float* qn, long Q, const void* dn, long N, int h, const SearchWs& w, char* ws,
+                  hipStream_t st) {
+  void* qd = ws + w.qd;
+  float* S = reinterpret_cast<float*>(ws + w.S);
+  if (dtype == TT_DT_BF16) TT_PROPAGATE(tt_cast(TT_DT_BF16, qn, Q * h, qd, st));
+  else TT_CHECK_HIP(hipMemcpyAsync(qd, qn, Q * h * 4, hipMemcpyDeviceToDevice, st));
+  tt_gemm_batch g{};
+  g.a[0] = qd; g.b[0] = dn; g.c[0] = S;
+  return tt_gemm(dtype, TT_DT_F32, 0, 0, (int)Q, (int)N, h, &g, 1, h, h, N, 1.f, 0, 0, 0, 0, 0.f, 1, nullptr, st);
 }
 
 template <int KM>
@@ -120,14 +141,8 @@ int search_launch(int dtype, const float* qn, long Q, const void* dn, long N, in
                          cv, ci);
     TT_CHECK_LAUNCH("search_scan_kernel");
   } else {
-    void* qd = ws + w.qd;
     float* S = reinterpret_cast<float*>(ws + w.S);
-    if (dtype == TT_DT_BF16) TT_PROPAGATE(tt_cast(TT_DT_BF16, qn, Q * h, qd, st));
-    else TT_CHECK_HIP(hipMemcpyAsync(qd, qn, Q * h * 4, hipMemcpyDeviceToDevice, st));
-    tt_gemm_batch g{};
-    g.a[0] = qd; g.b[0] = dn; g.c[0] = S;
-    TT_PROPAGATE(tt_gemm(dtype, TT_DT_F32, 0, 0, (int)Q, (int)N, h, &g, 1, h, h, N, 1.f, 0, 0, 0, 0, 0.f, 1, nullptr,
-                         st));
+    TT_PROPAGATE(search_scores(dtype, qn, Q, dn, N, h, w, ws, st));
     const long chunk = ttk::split_chunk(Q, N), nsp = tt_ceil_div(N, chunk);
     ncand = nsp * k;
     hipLaunchKernelGGL((ttk::topk_split_kernel<KM>), dim3((unsigned)tt_ceil_div(Q, 4), (unsigned)nsp), dim3(256), 0,
@@ -149,13 +164,19 @@ extern "C" long tt_search_ws_size(int dtype, long Q, long N, int h, int k) {
 extern "C" int tt_search_topk(int dtype, const float* qn, long Q, const void* dn, long N, int h, int k, int32_t* idx,
                               float* val, void* ws, void* stream) {
   TT_CHECK_ARG(dtype == TT_DT_F32 || dtype == TT_DT_BF16, "tt_search_topk: bad dtype");
-  TT_CHECK_ARG(k >= 1 && k <= SK_MAX && k <= N, "tt_search_topk: k=%d (N=%ld)", k, N);
+  TT_CHECK_ARG(k >= 1 && k <= ttk::SEL_MAX && k <= N, "tt_search_topk: k=%d needs 1 <= k <= min(%d, N=%ld)", k,
+               ttk::SEL_MAX, N);
   TT_CHECK_ARG(h > 0 && h % 8 == 0, "tt_search_topk: h=%d must be a multiple of 8", h);
   TT_CHECK_ARG(N <= INT_MAX && Q >= 0 && Q <= 65535L * 4, "tt_search_topk: N=%ld Q=%ld", N, Q);
   TT_CHECK_ARG(((uintptr_t)dn | (uintptr_t)qn) % 16 == 0, "tt_search_topk: operands must be 16-byte aligned");
   if (Q == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   char* ws_c = static_cast<char*>(ws);
+  if (k > SK_MAX) {  // the GEMM's scores for every Q, then the radix selection
+    const SearchWs w = search_ws(dtype, Q, N, h, k);
+    TT_PROPAGATE(search_scores(dtype, qn, Q, dn, N, h, w, ws_c, st));
+    return tt_topk_rows(reinterpret_cast<const float*>(ws_c + w.S), Q, N, N, -1L, k, idx, val, ws_c + w.sel, stream);
+  }
   if (k <= 4) return search_launch<4>(dtype, qn, Q, dn, N, h, k, idx, val, ws_c, st);
   return search_launch<SK_MAX>(dtype, qn, Q, dn, N, h, k, idx, val, ws_c, st);
 }

@@ -8,7 +8,8 @@
 
 namespace ttk {
 
-constexpr int SK_MAX = 16;
+constexpr int SK_MAX = 16;     // per-lane sorted lists (this file)
+constexpr int SEL_MAX = 1024;  // radix select over a stored score block (tt_select.hip)
 
 TT_DEV bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 

@@ -169,26 +169,38 @@ class MarginRankingLoss(nn.Module):
         return s / B
 
 
+MINE_SCAN_K = 16  # ttk::SK_MAX: above it tt_hardneg_topk stores the score block for every shape
+
+
 def mine_hard_negatives(query_vecs: torch.Tensor, doc_vecs: torch.Tensor, label_offset: int = 0, k: int = 5,
                         compute_dtype=torch.float32, eps: float = 1e-8, return_values: bool = False):
     """Batched get_hard_negatives: for row i the positive is doc label_offset + i (masked
     to -1; label_offset < 0 masks nothing). Returns int32 [B, k] sorted by descending
-    cosine, ties towards the lower doc index."""
+    cosine, ties towards the lower doc index. 1 <= k <= min(tt_topk_max() = 1024, docs);
+    above MINE_SCAN_K the scores are stored and radix-selected (tt_topk_rows), at most
+    1 GiB of score block per call."""
     _lib.require_gpu(query_vecs, doc_vecs)
+    lib = _lib.load()
+    B, nd = query_vecs.shape[0], doc_vecs.shape[0]
+    if not 1 <= k <= min(_lib.topk_max(), nd):
+        raise _lib.TTError(f"mine_hard_negatives: k={k} needs 1 <= k <= min({_lib.topk_max()}, {nd} docs)")
+    # rows per call: all of them, or for k > MINE_SCAN_K what keeps the score block within 1 GiB
+    step = max(B, 1) if k <= MINE_SCAN_K else max(1, min(B, (1 << 28) // nd))
     with torch.no_grad():
         qn, _, _ = ops.l2norm_fwd(query_vecs.float().contiguous(), eps, compute_dtype, want_f32=False)
         dn, _, _ = ops.l2norm_fwd(doc_vecs.float().contiguous(), eps, compute_dtype, want_f32=False)
-        B, h = qn.shape
-        nd = dn.shape[0]
+        h = qn.shape[1]
         idx = torch.empty(B, k, dtype=torch.int32, device=qn.device)
         val = torch.empty(B, k, dtype=torch.float32, device=qn.device) if return_values else None
-        lib = _lib.load()
-        ws = torch.empty(lib.tt_hardneg_ws_size(dtype_code(compute_dtype), B, nd, h, k), dtype=torch.uint8,
-                         device=qn.device)
         esz = 2 if compute_dtype == torch.bfloat16 else 4
-        with timing.region("hardneg_topk", 1, 2.0 * B * nd * h, float(esz * (B + nd) * h + B * k * 4)):
-            call("tt_hardneg_topk", dtype_code(compute_dtype), qn.data_ptr(), B, dn.data_ptr(), nd, h,
-                 label_offset, k, idx.data_ptr(), ptr(val), ws.data_ptr(), stream_ptr(qn.device))
+        dc = dtype_code(compute_dtype)
+        for r0 in range(0, B, step):
+            n = min(B, r0 + step) - r0
+            ws = torch.empty(lib.tt_hardneg_ws_size(dc, n, nd, h, k), dtype=torch.uint8, device=qn.device)
+            with timing.region("hardneg_topk", 1, 2.0 * n * nd * h, float(esz * (n + nd) * h + n * k * 4)):
+                call("tt_hardneg_topk", dc, qn[r0:].data_ptr(), n, dn.data_ptr(), nd, h,
+                     label_offset + r0 if label_offset >= 0 else label_offset, k, idx[r0:].data_ptr(),
+                     ptr(val[r0:]) if return_values else None, ws.data_ptr(), stream_ptr(qn.device))
     return (idx, val) if return_values else idx
 
 

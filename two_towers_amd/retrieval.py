@@ -51,3 +51,16 @@ def mrr_at_k(top_idx: torch.Tensor, relevant: Sequence[set]) -> float:
                 total += 1.0 / rank
                 break
     return total / max(len(rows), 1)
+
+
+def recall_at_k(top_idx: torch.Tensor, relevant: Sequence[set], ks: Sequence[int] = (1, 3, 10)) -> dict:
+    """{k: share of queries with a relevant document within the first k of top_idx}
+    (compare_models.py:60-84, R@1 / R@3 / R@10); k beyond top_idx's width counts the whole row."""
+    rows = top_idx.cpu().tolist()
+    hits = {int(k): 0 for k in ks}
+    for row, rel in zip(rows, relevant):
+        first = next((rank for rank, j in enumerate(row, 1) if j in rel), None)
+        if first is not None:
+            for k in hits:
+                hits[k] += first <= k
+    return {k: n / max(len(rows), 1) for k, n in hits.items()}

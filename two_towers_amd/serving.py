@@ -12,7 +12,8 @@ SearchIndex does the same on the HIP path, laid out for serving:
   - the cached matrix is stored already L2-normalised (eps 1e-8, F.cosine_similarity's)
     in the scoring dtype and stays resident in HBM, so a request is one query encode,
     one fused pass over the resident matrix (tt_search_topk: per-lane scores and top-k,
-    no score matrix, for up to 64 queries at once; a GEMM + column-split top-k beyond);
+    no score matrix, for up to 64 queries at once; a GEMM + column-split top-k beyond;
+    for top_k of 17 to 1024 a GEMM into a score block + an exact radix selection);
   - ties rank the lower document index first (torch.topk leaves them unspecified).
 
 make_app(index) builds the FastAPI app with the reference's request/response models
@@ -28,6 +29,7 @@ from ._lib import call, dtype_code, stream_ptr
 
 COS_EPS = 1e-8  # F.cosine_similarity default
 TOP_K = 3  # app.py:100
+SCAN_K = 16  # above it tt_search_topk stores the score block and radix-selects (tt_topk_rows)
 
 
 def snippet(text: str) -> str:
@@ -102,16 +104,21 @@ class SearchIndex:
         (indices int64 [Q, k], scores fp32 [Q, k])."""
         _lib.require_gpu(query_vecs)
         nd = self.doc_normed.shape[0]
-        if not 1 <= k <= min(16, nd):
-            raise ValueError(f"top_k={k} needs 1 <= k <= min(16, {nd})")
+        lib = _lib.load()
+        kmax = _lib.topk_max()
+        if not 1 <= k <= min(kmax, nd):
+            raise ValueError(f"top_k={k} needs 1 <= k <= min({kmax}, {nd} documents)")
         qn, _, _ = ops.l2norm_fwd(query_vecs.float().contiguous(), COS_EPS, torch.float32)
         Q, h = qn.shape
         idx = torch.empty(Q, k, dtype=torch.int32, device=qn.device)
         val = torch.empty(Q, k, dtype=torch.float32, device=qn.device)
-        lib = _lib.load()
         dc = dtype_code(self.score_dtype)
-        # large query batches go through a score block of at most 4 GiB per chunk
-        step = Q if Q <= 64 else max(65, min(Q, (1 << 30) // max(nd, 1)))
+        if k > SCAN_K:
+            # every query goes through a stored score block: at most 1 GiB of it per call
+            step = max(1, min(Q, (1 << 28) // max(nd, 1)))
+        else:
+            # large query batches go through a score block of at most 4 GiB per chunk
+            step = Q if Q <= 64 else max(65, min(Q, (1 << 30) // max(nd, 1)))
         esz = 2 if self.score_dtype == torch.bfloat16 else 4
         for r0 in range(0, Q, step):
             r1 = min(Q, r0 + step)

@@ -42,7 +42,8 @@ const char* tt_last_error(void);
  * of the same name in upper case with a TT_ prefix, e.g. gru_step <- TT_GRU_STEP):
  * GRU: gru_step, gru_depth, gru_bwd_rows, gru_bwd_big, gru_bwd_streams, gru_bwd_persist,
  * gru_bwd_skew, gru_fwd_step_rows, gru_fwd_xc, gru_fwd_xs, gru_fwd_skew, gru_xc_coop,
- * gru_step_ring; GEMM: gemm_persist, gemm_persist_maxk, gemm_a3, gemm_buf, gemm_bres,
+ * gru_step_ring, gru_yprev (read by the callers of tt_gru_fwd_yprev, not by the kernels:
+ * whether the training step uses the previous-state layout where it is supported); GEMM: gemm_persist, gemm_persist_maxk, gemm_a3, gemm_buf, gemm_bres,
  * bres_rows, bres_form, wgrad_tall, gemm_iepi, gemm_order, gemm_skew, gemm_regstage, gemm_stream_out; losses:
  * hn_gemm, hn_map, hn_scan_gemm, infonce_flash; diagnostics gru_xc_skip, gru_xc_spins. The authoritative list with
  * defaults is kOpts in two_towers_amd/csrc/tt_gemm.hip. Every variant computes the same
@@ -252,6 +253,27 @@ int tt_gru_bwd_launches(int dtype, int T, int H);
  * carry bytes in HBM), 0 when it round-trips a bf16 / fp32 carry buffer (dhstate). */
 int tt_gru_bwd_carry_on_chip(int dtype, int T, int H);
 int tt_gru_bias_rows(int B);
+
+/* Previous-state layout of the layer output. Apart from the final state, every reader of a
+ * training layer's output wants the state a step STARTS from: the BPTT epilogue (h_{s-1}) and
+ * dW_hh = sum_t dL/dgh[t]^T h[t-1]. tt_gru_fwd_yprev is tt_gru_fwd with y stored that way:
+ *   dir 0: y[b, t] = h[b, t-1], zeros at t = 0;   dir 1: y[b, t] = h[b, t+1], zeros at t = T-1
+ * (the zero rows are written by the call), and the state after the last step goes to
+ * hfinal[i][b*ldf + j] (dtype; one pointer per record, or hfinal NULL: not wanted), as
+ * tt_gru_fwd_infer's hfinal. save, x1 (at its own time index), the dropout draw and every
+ * value computed are tt_gru_fwd's: h_t is bit for bit what tt_gru_fwd stores at row t. With
+ * it dW_hh is a plain TN tt_gemm on y (no bshift / seq_t) with the same sums in the same
+ * order, and tt_gru_bwd_yprev is tt_gru_bwd reading h_{s-1} at row t of that y.
+ * Implemented by the column-split forward kernels (gru_fwd_xs, gru_fwd_xcp: bf16, H 256 /
+ * 512, a tt_gru_fwd_ws_size workspace) and the row-owning backward (gru_bwd_rows);
+ * tt_gru_yprev_supported says whether both apply to a call shape on the current device under
+ * the current options. Where they do not, the two entry points return TT_EINVAL (they never
+ * fall back to another layout) and the caller uses tt_gru_fwd / tt_gru_bwd. */
+int tt_gru_yprev_supported(int dtype, int nrec, int B, int T, int H, long ldg, long ldy);
+int tt_gru_fwd_yprev(int dtype, const tt_gru_fwd_rec* recs, void* const* hfinal, int nrec, int B, int T, int H,
+                     long ldg, long ldy, long ldf, float drop_p, void* ws, long ws_bytes, void* stream);
+int tt_gru_bwd_yprev(int dtype, const tt_gru_bwd_rec* recs, int nrec, int B, int T, int H, long ldy,
+                     long ldd, long ldf, void* stream);
 
 /* ------------------------------------------------------------ projection head */
 /* Linear(4h->2h) -> LayerNorm(2h, eps) -> ReLU -> Linear(2h->h), fwd and bwd.

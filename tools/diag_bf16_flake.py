@@ -19,7 +19,7 @@ _orig_fwd = towers._gru_layer_fwd if hasattr(towers, "_gru_layer_fwd") else None
 LOG = []
 
 
-def _bwd_probe(cfg, layer, B, T, S, Y, dY, dfinal, packs):
+def _bwd_probe(cfg, layer, B, T, S, Y, dY, dfinal, packs, **kw):
     # inputs of the layer's BPTT and its outputs: report rows holding |x| > 1e6
     torch.cuda.synchronize()
     ins = {}
@@ -29,7 +29,7 @@ def _bwd_probe(cfg, layer, B, T, S, Y, dY, dfinal, packs):
         ins["Y%d" % ti] = Y[ti]
         if dY is not None:
             ins["dY%d" % ti] = dY[ti]
-    dG, dbih, dbhh = _orig_bwd(cfg, layer, B, T, S, Y, dY, dfinal, packs)
+    dG, dbih, dbhh = _orig_bwd(cfg, layer, B, T, S, Y, dY, dfinal, packs, **kw)
     torch.cuda.synchronize()
     for ti in range(len(dG)):
         ins["dG%d" % ti] = dG[ti]

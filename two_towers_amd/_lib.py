@@ -145,6 +145,11 @@ _SIGS = {
     "tt_gru_fwd_infer": (c_int, [c_int, POINTER(GruInferRec), c_int, c_int, c_int, c_int, c_long, c_long, c_long,
                                  c_void_p, c_long, c_void_p]),
     "tt_gru_infer_scratch_size": (c_long, [c_int, c_int, c_int, c_int, c_int]),
+    "tt_gru_yprev_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_long, c_long]),
+    "tt_gru_fwd_yprev": (c_int, [c_int, POINTER(GruFwdRec), POINTER(c_void_p), c_int, c_int, c_int, c_int, c_long,
+                                 c_long, c_long, c_float, c_void_p, c_long, c_void_p]),
+    "tt_gru_bwd_yprev": (c_int, [c_int, POINTER(GruBwdRec), c_int, c_int, c_int, c_int, c_long, c_long, c_long,
+                                 c_void_p]),
     "tt_proj_head_fwd": (c_int, [c_int, POINTER(HeadFwdIO), c_int, c_int, c_int, c_float, c_void_p]),
     "tt_proj_head_bwd": (c_int, [c_int, POINTER(HeadBwdIO), c_int, c_int, c_int, c_float, c_void_p]),
     "tt_proj_head_bwd_ws_size": (c_long, [c_int, c_int, c_int]),

@@ -52,6 +52,8 @@ enum Opt {
   OPT_WGRAD_TALL,       // 1: bf16 TN products with 256 < M <= 320 (layer-0 dW_ih^T) on one 320-row tile per
                         // column panel (gemm_tall) instead of a 256-row tile and a tail tile, a thin last
                         // round as half tiles (2: whole tiles only, 3: half tiles only; 0: off)
+  OPT_GRU_YPREV,        // 1: the training step stores the GRU layer outputs in the previous-state layout
+                        // (tt_gru_fwd_yprev) where tt_gru_yprev_supported, so dW_hh is a plain TN GEMM; 0: Y as h_t
   OPT_N
 };
 int opt(Opt o);

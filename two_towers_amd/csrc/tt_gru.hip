@@ -43,11 +43,21 @@ struct InfArgs : FwdArgs {
   void* himg[4];
   long ldf;
 };
+// Arguments of the training kernels in the previous-state layout (tt_gru_fwd_yprev): the Y
+// store of step s goes to the row of the step that starts from it (t + 1, or t - 1 for
+// dir 1), and the last step's, which has no such row, to the [B, ldf] final-state output
+// (or nowhere: hfin null).
+struct YpArgs : FwdArgs {
+  void* hfin[4];
+  long ldf;
+};
 // what the shared kernel bodies read of them outside `if constexpr (INF)`
 TT_DEV void* inf_hfin(const FwdArgs&, int) { return nullptr; }
 TT_DEV void* inf_hfin(const InfArgs& a, int rz) { return a.hfin[rz]; }
+TT_DEV void* inf_hfin(const YpArgs& a, int rz) { return a.hfin[rz]; }
 TT_DEV long inf_ldf(const FwdArgs&) { return 0; }
 TT_DEV long inf_ldf(const InfArgs& a) { return a.ldf; }
+TT_DEV long inf_ldf(const YpArgs& a) { return a.ldf; }
 
 struct BwdRec {
   const void* save; const void* y; const void* dy; const float* dfinal; const void* whh;
@@ -59,6 +69,7 @@ struct BwdArgs {
   long ldy, ldd, ldf;
   int s;
   int skew;  // gru_bwd_rows: odd workgroups of an XCD start skew x s_sleep(127) late (option gru_bwd_skew)
+  int yprev;  // gru_bwd_rows: y is in the previous-state layout (tt_gru_bwd_yprev): h_{s-1} is its row t
 #ifdef TT_DIAG
   int dbg;  // diagnostic build only: 1 no GEMM, 2 no epilogue loads, 4 no stores
 #endif
@@ -900,7 +911,8 @@ __global__ __launch_bounds__(512) void gru_bwd_rows(BwdArgs a) {
     bf16_t* cr_cur = static_cast<bf16_t*>(R.dh) + (long)(s & 1) * a.B * H + (long)m0 * H;
     const __amdgpu_buffer_rsrc_t rd = tt_rsrc_n(DY ? DY + trow * a.ldy : S, DY != nullptr);
     const __amdgpu_buffer_rsrc_t rsv = tt_rsrc_n(S + trow * 4L * H, true);
-    const __amdgpu_buffer_rsrc_t ry = tt_rsrc_n(s > 0 ? Y + ((long)m0 * T_ + tp) * a.ldy : S, s > 0);
+    // h_{s-1}: row tp of Y, or row t of a Y in the previous-state layout
+    const __amdgpu_buffer_rsrc_t ry = tt_rsrc_n(s > 0 ? Y + ((long)m0 * T_ + (a.yprev ? t : tp)) * a.ldy : S, s > 0);
     const __amdgpu_buffer_rsrc_t grs = tt_rsrc(DGXw + trow * a.ldd);
     uint32_t* L16 = reinterpret_cast<uint32_t*>(lds);
     // the accumulator as a bf16 image: one 8-byte store of 4 units per (row block, column block)
@@ -1596,6 +1608,7 @@ TT_DEV void xc_stage(float* stg, const f32x4 (&acc)[2][3]) {
 template <int H, bool DROP, typename A = FwdArgs>
 __global__ __launch_bounds__(xc::NT, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) void gru_fwd_xcp(A a, XcWs ws) {
   constexpr bool INF = std::is_same_v<A, InfArgs>;  // the inference form (tt_gru_fwd_infer)
+  constexpr bool YP = std::is_same_v<A, YpArgs>;    // Y in the previous-state layout (tt_gru_fwd_yprev)
   static_assert(!(INF && DROP), "no dropout copy in the inference form");
   using C = xc::Cfg<H>;
   constexpr int M = C::M, NKT = C::NKT;
@@ -1723,14 +1736,23 @@ __global__ __launch_bounds__(xc::NT, 1) __attribute__((amdgpu_waves_per_eu(1, 1)
     const long r0w = (long)(cur.nrow > 0 ? cur.rb0 : 0) * T_;
     const bool on = cur.nrow > 0;
     bf16_t* HF = static_cast<bf16_t*>(inf_hfin(a, rz));
-    const __amdgpu_buffer_rsrc_t rY =
+    __amdgpu_buffer_rsrc_t rY =
         INF ? tt_rsrc_n(Yw ? (const void*)(Yw + r0w * a.ldy) : G, on && Yw != nullptr) : tt_rsrc_n(Yw + r0w * a.ldy, on);
+    // YP: the Y slot of a round's last step carries h to hfin (dropped where hfin is null)
+    [[maybe_unused]] const bool ylast = YP && cur.s == T_ - 1;
+    if constexpr (YP) {
+      if (ylast) rY = tt_rsrc_n(HF ? (const void*)(HF + (long)(on ? cur.rb0 : 0) * inf_ldf(a)) : G, on && HF != nullptr);
+    }
     const __amdgpu_buffer_rsrc_t rX1 =
         INF ? tt_rsrc_n(HF ? (const void*)(HF + (long)(on ? cur.rb0 : 0) * inf_ldf(a)) : G, on && HF != nullptr && cur.s == T_ - 1)
             : tt_rsrc_n(X1 ? X1 + r0w * a.ldy : Yw, on && X1 != nullptr);
     const __amdgpu_buffer_rsrc_t rS = INF ? tt_rsrc_n(G, false) : tt_rsrc_n(S + r0w * 4L * H, on);
     const __amdgpu_buffer_rsrc_t rdst_h = rx[idx & 1];
     const int t = cur.t;
+    // YP: element offset of chunk row rr's Y store = rr * ypr + ypo (the next step's row of
+    // Y, or row rr of the final-state output)
+    [[maybe_unused]] const int ypr = ylast ? (int)inf_ldf(a) : T_ * (int)a.ldy;
+    [[maybe_unused]] const int ypo = ylast ? 0 : (R.dir ? t - 1 : t + 1) * (int)a.ldy;
 #pragma unroll
     for (int c = 0; c < xc::NCH; ++c) {
       const bool more = c + 1 < xc::NCH || has_next;  // a chunk follows in the stream
@@ -1811,7 +1833,8 @@ __global__ __launch_bounds__(xc::NT, 1) __attribute__((amdgpu_waves_per_eu(1, 1)
         const uint32_t os = ok ? (uint32_t)(lrow * 4 * H + j) * 2u : xc::OOB;
         // outputs: read only by later kernels (cache policy XC_OUT_AUX; offsets folded into
         // the lane offset, soffset 0, as st16_buf does)
-        st16_buf_aux<XC_OUT_AUX>(rY, (int)oy, yb);
+        if constexpr (YP) st16_buf_aux<XC_OUT_AUX>(rY, (int)(ok ? (uint32_t)(rr * ypr + ypo + j) * 2u : xc::OOB), yb);
+        else st16_buf_aux<XC_OUT_AUX>(rY, (int)oy, yb);
         if constexpr (INF) {
           st16_buf_aux<XC_OUT_AUX>(rS, (int)os, yb);
           st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 2u * H), yb);
@@ -1902,6 +1925,7 @@ static_assert(Cfg<512>::LDS <= 163840, "gru_fwd_xs LDS budget");
 template <int H, bool DROP, typename A = FwdArgs>
 __global__ __launch_bounds__(xs::NT, 1) __attribute__((amdgpu_waves_per_eu(2, 2))) void gru_fwd_xs(A a, XcWs ws) {
   constexpr bool INF = std::is_same_v<A, InfArgs>;  // the inference form (tt_gru_fwd_infer)
+  constexpr bool YP = std::is_same_v<A, YpArgs>;    // Y in the previous-state layout, as in gru_fwd_xcp
   static_assert(!(INF && DROP), "no dropout copy in the inference form");
   using C = xc::Cfg<H>;
   constexpr int M = C::M, NKT = C::NKT, QPW = C::QPW;
@@ -2089,14 +2113,23 @@ __global__ __launch_bounds__(xs::NT, 1) __attribute__((amdgpu_waves_per_eu(2, 2)
     const long r0w = (long)(cur.nrow > 0 ? cur.rb0 : 0) * T_;
     const bool on = cur.nrow > 0;
     bf16_t* HF = static_cast<bf16_t*>(inf_hfin(a, rz));
-    const __amdgpu_buffer_rsrc_t rY =
+    __amdgpu_buffer_rsrc_t rY =
         INF ? tt_rsrc_n(Yw ? (const void*)(Yw + r0w * a.ldy) : G, on && Yw != nullptr) : tt_rsrc_n(Yw + r0w * a.ldy, on);
+    // YP: the Y slot of a round's last step carries h to hfin (dropped where hfin is null)
+    [[maybe_unused]] const bool ylast = YP && cur.s == T_ - 1;
+    if constexpr (YP) {
+      if (ylast) rY = tt_rsrc_n(HF ? (const void*)(HF + (long)(on ? cur.rb0 : 0) * inf_ldf(a)) : G, on && HF != nullptr);
+    }
     const __amdgpu_buffer_rsrc_t rX1 =
         INF ? tt_rsrc_n(HF ? (const void*)(HF + (long)(on ? cur.rb0 : 0) * inf_ldf(a)) : G, on && HF != nullptr && cur.s == T_ - 1)
             : tt_rsrc_n(X1 ? X1 + r0w * a.ldy : Yw, on && X1 != nullptr);
     const __amdgpu_buffer_rsrc_t rS = INF ? tt_rsrc_n(G, false) : tt_rsrc_n(S + r0w * 4L * H, on);
     const __amdgpu_buffer_rsrc_t rdst_h = rx[idx & 1];
     const int t = cur.t;
+    // YP: element offset of chunk row rr's Y store = rr * ypr + ypo (the next step's row of
+    // Y, or row rr of the final-state output)
+    [[maybe_unused]] const int ypr = ylast ? (int)inf_ldf(a) : T_ * (int)a.ldy;
+    [[maybe_unused]] const int ypo = ylast ? 0 : (R.dir ? t - 1 : t + 1) * (int)a.ldy;
     const bool first = cur.s == 0;
 #pragma unroll
     for (int c = 0; c < xc::NCH; ++c) {
@@ -2140,7 +2173,8 @@ __global__ __launch_bounds__(xs::NT, 1) __attribute__((amdgpu_waves_per_eu(2, 2)
         const bool okd = ok && !(dbg & 1);
         const uint32_t oy = okd ? (uint32_t)(lrow * (int)a.ldy + j) * 2u : xc::OOB;
         const uint32_t os = okd ? (uint32_t)(lrow * 4 * H + j) * 2u : xc::OOB;
-        st16_buf_aux<XC_OUT_AUX>(rY, (int)oy, yb);
+        if constexpr (YP) st16_buf_aux<XC_OUT_AUX>(rY, (int)(okd ? (uint32_t)(rr * ypr + ypo + j) * 2u : xc::OOB), yb);
+        else st16_buf_aux<XC_OUT_AUX>(rY, (int)oy, yb);
         if constexpr (INF) {
           st16_buf_aux<XC_OUT_AUX>(rS, (int)os, yb);
           st16_buf_aux<XC_OUT_AUX>(rS, (int)(os + 2u * H), yb);
@@ -2286,6 +2320,8 @@ struct XcDev {
   int occ_xs[2] = {0, 0};            // gru_fwd_xs<512, DROP>
   int occ_inf[2] = {0, 0};           // gru_fwd_xcp<256 / 512, false, InfArgs>
   int occ_xs_inf = 0;                // gru_fwd_xs<512, false, InfArgs>
+  int occ_yp[2][2] = {{0, 0}, {0, 0}};  // gru_fwd_xcp<256 / 512, DROP, YpArgs>
+  int occ_xs_yp[2] = {0, 0};            // gru_fwd_xs<512, DROP, YpArgs>
 };
 static std::mutex g_xc_mu;
 static XcDev g_xc[64];
@@ -2303,6 +2339,14 @@ static const void* xc_infer_kernel() {
   return reinterpret_cast<const void*>(&gru_fwd_xcp<H, false, InfArgs>);
 }
 static const void* xs_infer_kernel() { return reinterpret_cast<const void*>(&gru_fwd_xs<512, false, InfArgs>); }
+template <int H, bool DROP>
+static const void* xc_yprev_kernel() {
+  return reinterpret_cast<const void*>(&gru_fwd_xcp<H, DROP, YpArgs>);
+}
+template <bool DROP>
+static const void* xs_yprev_kernel() {
+  return reinterpret_cast<const void*>(&gru_fwd_xs<512, DROP, YpArgs>);
+}
 // the specialized-wave form (gru_fwd_xs) where it is selected and built (H 512)
 static bool xs_on(int H) { return H == 512 && tt::opt(tt::OPT_GRU_FWD_XS) != 0; }
 
@@ -2324,6 +2368,12 @@ static int xc_device(XcDev** out) {
     const void* ki[2] = {xc_infer_kernel<256>(), xc_infer_kernel<512>()};
     for (int h = 0; h < 2; ++h) TT_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&x.occ_inf[h], ki[h], xc::NT, 0));
     TT_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&x.occ_xs_inf, xs_infer_kernel(), xs::NT, 0));
+    const void* ky[2][2] = {{xc_yprev_kernel<256, false>(), xc_yprev_kernel<256, true>()},
+                            {xc_yprev_kernel<512, false>(), xc_yprev_kernel<512, true>()}};
+    for (int h = 0; h < 2; ++h)
+      for (int d = 0; d < 2; ++d) TT_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&x.occ_yp[h][d], ky[h][d], xc::NT, 0));
+    const void* kxy[2] = {xs_yprev_kernel<false>(), xs_yprev_kernel<true>()};
+    for (int d = 0; d < 2; ++d) TT_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&x.occ_xs_yp[d], kxy[d], xs::NT, 0));
     x.cus = cus;
   }
   *out = &x;
@@ -2332,7 +2382,7 @@ static int xc_device(XcDev** out) {
 
 // Launch geometry of the column-split forward, or false where it does not apply.
 static bool xc_geometry(const XcDev& dev, int dtype, int H, int nrec, int B, int T, long ldg, long ldy, bool drop,
-                        XcGeo& g, bool inf = false) {
+                        XcGeo& g, bool inf = false, bool yp = false) {
   const int v = tt::opt(tt::OPT_GRU_FWD_XC);
   if (v == 0 || dtype != TT_DT_BF16 || (H != 512 && H != 256) || tt::opt(tt::OPT_GRU_STEP) == 1) return false;
   const int M = H / 64;
@@ -2340,8 +2390,9 @@ static bool xc_geometry(const XcDev& dev, int dtype, int H, int nrec, int B, int
   const int ng = 8 * qg;
   if (qg < 1 || ng > XC_MAX_GROUPS || ng % nrec != 0) return false;
   // every member must be resident at once: one workgroup per CU, grid <= CUs
-  const int occ = inf ? (xs_on(H) ? dev.occ_xs_inf : dev.occ_inf[H == 512])
-                      : (xs_on(H) ? dev.occ_xs[drop] : dev.occ[H == 512][drop]);
+  const int occ = inf  ? (xs_on(H) ? dev.occ_xs_inf : dev.occ_inf[H == 512])
+                  : yp ? (xs_on(H) ? dev.occ_xs_yp[drop] : dev.occ_yp[H == 512][drop])
+                       : (xs_on(H) ? dev.occ_xs[drop] : dev.occ[H == 512][drop]);
   if (occ < 1 || ng * M > dev.cus * occ) return false;
   const int gpr = ng / nrec;
   // auto mode: only where every group gets at least half a round of rows
@@ -2367,14 +2418,14 @@ static bool xc_geometry(const XcDev& dev, int dtype, int H, int nrec, int B, int
 }
 
 static int xc_plan(int dtype, int nrec, int B, int T, int H, long ldg, long ldy, bool drop, XcGeo& g, bool* ok,
-                   bool inf = false) {
+                   bool inf = false, bool yp = false) {
   *ok = false;
   if (dtype != TT_DT_BF16 || nrec < 1 || nrec > 4 || B <= 0 || T <= 0 || (H != 256 && H != 512) ||
       tt::opt(tt::OPT_GRU_FWD_XC) == 0)
     return 0;
   XcDev* x = nullptr;
   TT_PROPAGATE(xc_device(&x));
-  *ok = xc_geometry(*x, dtype, H, nrec, B, T, ldg, ldy, drop, g, inf);
+  *ok = xc_geometry(*x, dtype, H, nrec, B, T, ldg, ldy, drop, g, inf, yp);
   return 0;
 }
 
@@ -2389,16 +2440,16 @@ extern "C" long tt_gru_fwd_ws_size(int dtype, int nrec, int B, int T, int H, lon
 
 // Launches the column-split forward when it applies and ws is large enough (*used = true);
 // a grid the runtime will not make co-resident leaves *used false (row-owning fallback).
-template <typename A>  // FwdArgs: the training kernels; InfArgs: the inference kernels
+template <typename A>  // FwdArgs: the training kernels; InfArgs: the inference kernels; YpArgs: previous-state Y
 static int gru_fwd_xc_launch(const A& a, int nrec, int B, int T, int H, long ldg, long ldy, void* ws,
                              long ws_bytes, hipStream_t st, bool* used) {
-  constexpr bool inf = std::is_same_v<A, InfArgs>;
+  constexpr bool inf = std::is_same_v<A, InfArgs>, yp = std::is_same_v<A, YpArgs>;
   *used = false;
   if (!ws) return 0;
   const bool drop = !inf && a.drop_thresh != 0 && a.r[0].x1 != nullptr;
   XcGeo g;
   bool ok = false;
-  TT_PROPAGATE(xc_plan(TT_DT_BF16, nrec, B, T, H, ldg, ldy, drop, g, &ok, inf));
+  TT_PROPAGATE(xc_plan(TT_DT_BF16, nrec, B, T, H, ldg, ldy, drop, g, &ok, inf, yp));
   if (!ok || ws_bytes < g.bytes) return 0;
   TT_CHECK_ARG(((uintptr_t)ws & 255) == 0, "tt_gru_fwd: ws must be 256-byte aligned");
   char* base = static_cast<char*>(ws);
@@ -2412,6 +2463,9 @@ static int gru_fwd_xc_launch(const A& a, int nrec, int B, int T, int H, long ldg
   void* args[] = {&ak, &wk};
   const bool xs = xs_on(H);
   const void* fn = inf ? (xs ? xs_infer_kernel() : H == 512 ? xc_infer_kernel<512>() : xc_infer_kernel<256>())
+                   : yp ? (xs ? (drop ? xs_yprev_kernel<true>() : xs_yprev_kernel<false>())
+                           : H == 512 ? (drop ? xc_yprev_kernel<512, true>() : xc_yprev_kernel<512, false>())
+                                      : (drop ? xc_yprev_kernel<256, true>() : xc_yprev_kernel<256, false>()))
                    : xs ? (drop ? xs_kernel<true>() : xs_kernel<false>())
                    : H == 512 ? (drop ? xc_kernel<512, true>() : xc_kernel<512, false>())
                               : (drop ? xc_kernel<256, true>() : xc_kernel<256, false>());
@@ -2536,6 +2590,78 @@ extern "C" int tt_gru_fwd(int dtype, const tt_gru_fwd_rec* recs, int nrec, int B
   return launch_fwd_steps(dtype, a, nrec, B, T, H, ldg, ldy, st);
 }
 
+// ---- previous-state layout of Y (tt_gru_fwd_yprev / tt_gru_bwd_yprev) -------------------
+namespace {
+// The rows of the layout that no step stores (t = 0 of a dir-0 recurrence, t = T-1 of a
+// dir-1 one: the state before the first step) <- zeros, 16 bytes per thread. The forward
+// kernels never write these rows, so the order of the two launches does not matter.
+struct YpZeroArgs {
+  void* y[4];
+  int dir[4];
+  int B, T, H;
+  long ldy;
+};
+__global__ __launch_bounds__(256) void gru_yprev_zero_rows(YpZeroArgs a) {
+  const int per = a.H / 8;  // 16-byte pieces of a row
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)a.B * per) return;
+  const int rz = blockIdx.y;
+  const long b = i / per;
+  const int j = (int)(i - b * per) * 8;
+  const int t = a.dir[rz] ? a.T - 1 : 0;
+  *reinterpret_cast<uint4*>(static_cast<bf16_t*>(a.y[rz]) + (b * a.T + t) * a.ldy + j) = make_uint4(0u, 0u, 0u, 0u);
+}
+}  // namespace
+
+extern "C" int tt_gru_yprev_supported(int dtype, int nrec, int B, int T, int H, long ldg, long ldy) {
+  if (!gru_bwd_persistent(dtype, H) || H > 512) return 0;
+  XcGeo g;
+  bool ok = false;
+  // the dropout and plain instances have the same geometry (as tt_gru_fwd_ws_size)
+  if (xc_plan(dtype, nrec, B, T, H, ldg, ldy, true, g, &ok, false, true) != 0 || !ok) return 0;
+  return 1;
+}
+
+extern "C" int tt_gru_fwd_yprev(int dtype, const tt_gru_fwd_rec* recs, void* const* hfinal, int nrec, int B, int T,
+                                int H, long ldg, long ldy, long ldf, float drop_p, void* ws, long ws_bytes,
+                                void* stream) {
+  TT_CHECK_ARG(dtype == TT_DT_BF16, "tt_gru_fwd_yprev: bf16 only (tt_gru_yprev_supported)");
+  TT_CHECK_ARG(nrec >= 1 && nrec <= 4, "tt_gru_fwd_yprev: nrec %d", nrec);
+  TT_CHECK_ARG(B > 0 && T > 0 && (H == 256 || H == 512), "tt_gru_fwd_yprev: bad shape (H 256 or 512)");
+  TT_CHECK_ARG(ws != nullptr && ws_bytes > 0, "tt_gru_fwd_yprev: needs the tt_gru_fwd_ws_size workspace");
+  TT_CHECK_ARG((ldy * 2) % 16 == 0 && ldy >= H, "tt_gru_fwd_yprev: ldy=%ld misaligned or below H", ldy);
+  TT_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, "tt_gru_fwd_yprev: drop_p");
+  TT_CHECK_ARG(128L * T * std::max({4L * H, ldy, ldg}) * 2 < (1L << 31), "tt_gru_fwd_yprev: tile byte offsets exceed 2 GiB");
+  TT_CHECK_ARG(!hfinal || (ldf >= H && (ldf * 2) % 16 == 0 && 256L * ldf * 2 < (1L << 31)),
+               "tt_gru_fwd_yprev: ldf=%ld misaligned or below H", ldf);
+  YpArgs a{};
+  YpZeroArgs z{};
+  for (int i = 0; i < nrec; ++i) {
+    const tt_gru_fwd_rec& r = recs[i];
+    TT_CHECK_ARG(r.g && r.whh && r.bhn && r.y && r.save, "tt_gru_fwd_yprev: null pointer in rec %d", i);
+    TT_CHECK_ARG(((uintptr_t)r.y & 15) == 0, "tt_gru_fwd_yprev: y of rec %d is not 16-byte aligned", i);
+    TT_CHECK_ARG(!hfinal || (hfinal[i] && ((uintptr_t)hfinal[i] & 15) == 0),
+                 "tt_gru_fwd_yprev: hfinal[%d] null or not 16-byte aligned", i);
+    a.r[i] = FwdRec{r.g, r.whh, r.bhn, r.y, r.x1, r.save, r.hstate, r.dir, r.drop_seed, r.drop_col0, r.drop_row0};
+    a.hfin[i] = hfinal ? hfinal[i] : nullptr;
+    z.y[i] = r.y;
+    z.dir[i] = r.dir;
+  }
+  a.B = B; a.T = T; a.H = H; a.ldg = ldg; a.ldy = ldy; a.ldf = hfinal ? ldf : 0;
+  a.drop_thresh = drop_p > 0.f ? (uint32_t)(drop_p * 16777216.0f + 0.5f) : 0u;
+  a.inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
+  z.B = B; z.T = T; z.H = H; z.ldy = ldy;
+  hipStream_t st = (hipStream_t)stream;
+  bool used = false;
+  TT_PROPAGATE(gru_fwd_xc_launch(a, nrec, B, T, H, ldg, ldy, ws, ws_bytes, st, &used));
+  // never another layout in place of the one asked for: the caller asks tt_gru_yprev_supported
+  TT_CHECK_ARG(used, "tt_gru_fwd_yprev: the column-split forward does not apply to this call (tt_gru_yprev_supported)");
+  hipLaunchKernelGGL(gru_yprev_zero_rows, dim3((unsigned)tt_ceil_div((long)B * (H / 8), 256), (unsigned)nrec), dim3(256), 0,
+                     st, z);
+  TT_CHECK_LAUNCH("gru_yprev_zero_rows");
+  return 0;
+}
+
 // ---- inference forward: no saved pre-activations, optionally only the final state ------
 extern "C" long tt_gru_infer_scratch_size(int dtype, int B, int T, int H, int final_only) {
   if ((dtype != TT_DT_F32 && dtype != TT_DT_BF16) || B <= 0 || T <= 0 || H <= 0) return 0;
@@ -2595,14 +2721,17 @@ static void launch_bwd_step(int ring, dim3 grid, hipStream_t st, const BwdArgs& 
   else hipLaunchKernelGGL((gru_bwd_step<T, BMR>), grid, dim3(256), 0, st, a);
 }
 
-extern "C" int tt_gru_bwd(int dtype, const tt_gru_bwd_rec* recs, int nrec, int B, int T, int H, long ldy,
-                          long ldd, long ldf, void* stream) {
+// yprev: recs[].y is in the previous-state layout (tt_gru_bwd_yprev; the row-owning kernel only)
+static int gru_bwd_impl(int dtype, const tt_gru_bwd_rec* recs, int nrec, int B, int T, int H, long ldy, long ldd,
+                        long ldf, void* stream, int yprev) {
   TT_CHECK_ARG(dtype == TT_DT_F32 || dtype == TT_DT_BF16, "tt_gru_bwd: bad dtype");
   TT_CHECK_ARG(nrec >= 1 && nrec <= 4, "tt_gru_bwd: nrec %d", nrec);
   TT_CHECK_ARG(B > 0 && T > 0 && H > 0, "tt_gru_bwd: bad shape");
   const int esz = dtype == TT_DT_BF16 ? 2 : 4;
   TT_CHECK_ARG(H % 8 == 0 && (ldd * esz) % 16 == 0, "tt_gru_bwd: H=%d (multiple of 8)/ldd=%ld misaligned", H, ldd);
   TT_CHECK_ARG(256L * T * std::max({ldd, ldy, 4L * H}) * esz < (1L << 31), "tt_gru_bwd: tile byte offsets exceed 2 GiB");
+  TT_CHECK_ARG(!yprev || (gru_bwd_persistent(dtype, H) && H <= 512),
+               "tt_gru_bwd_yprev: the row-owning backward does not apply to this call (tt_gru_yprev_supported)");
   hipStream_t st = (hipStream_t)stream;
   BwdArgs a{};
   for (int i = 0; i < nrec; ++i) {
@@ -2614,6 +2743,7 @@ extern "C" int tt_gru_bwd(int dtype, const tt_gru_bwd_rec* recs, int nrec, int B
   }
   a.B = B; a.T = T; a.H = H; a.ldy = ldy; a.ldd = ldd; a.ldf = ldf;
   a.skew = tt::opt(tt::OPT_GRU_BWD_SKEW);
+  a.yprev = yprev;
 #ifdef TT_DIAG
   if (const char* e = getenv("TT_GRU_DBG")) a.dbg = atoi(e);
 #endif
@@ -2685,4 +2815,14 @@ extern "C" int tt_gru_bwd(int dtype, const tt_gru_bwd_rec* recs, int nrec, int B
     TT_CHECK_HIP(hipStreamWaitEvent(st, side->join, 0));
   }
   return 0;
+}
+
+extern "C" int tt_gru_bwd(int dtype, const tt_gru_bwd_rec* recs, int nrec, int B, int T, int H, long ldy,
+                          long ldd, long ldf, void* stream) {
+  return gru_bwd_impl(dtype, recs, nrec, B, T, H, ldy, ldd, ldf, stream, 0);
+}
+
+extern "C" int tt_gru_bwd_yprev(int dtype, const tt_gru_bwd_rec* recs, int nrec, int B, int T, int H, long ldy,
+                                long ldd, long ldf, void* stream) {
+  return gru_bwd_impl(dtype, recs, nrec, B, T, H, ldy, ldd, ldf, stream, 1);
 }

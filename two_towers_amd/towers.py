@@ -10,7 +10,9 @@ four recurrences.
 Layout in HBM (per tower; row = b*T + t, dt = compute dtype):
   X0  [B*T, Ep]  dt   layer-0 input (gathered Word2Vec rows / packed floats)
   G   [B*T, 6H]  dt   input projections, fwd gates r|z|n then rev gates
-  Y   [B*T, 2H]  dt   layer output h_t (fwd | rev), X1 = dropout(Y0) (layer-1 input)
+  Y   [B*T, 2H]  dt   layer output h_t (fwd | rev), X1 = dropout(Y0) (layer-1 input); with option
+                      gru_yprev the row of t holds h_{t-1} (fwd) | h_{t+1} (rev), zeros at a
+                      direction's first step, and the final states go to their own [B, 2H]
   S   [B*T, 4H]  dt   saved pre-activations of r|z|n and gh_n per direction
   dG  [B*T, 8H]  dt   gradients wrt gate pre-activations: dL/dg_x r|z|n (fwd, rev) in
                       [0, 6H), dL/d(W_hn h) (fwd, rev) in [6H, 8H); dL/dg_h shares r|z
@@ -306,10 +308,23 @@ def featurize(x: torch.Tensor, table: torch.Tensor | None, Ep: int, dt: torch.dt
     return out
 
 
-def _gru_layer_fwd(cfg, xs, K, ldx, packs, layer, B, T, seeds, want_x1, ws):
+def yprev_supported(cfg, B, T) -> bool:
+    """Whether the GRU layers of this call shape can store their output in the
+    previous-state layout (include/tt_hip.h tt_gru_fwd_yprev): option gru_yprev, and both the
+    forward and the backward kernel family the library would run implement it."""
+    H = cfg.H
+    if not _lib.get_option("gru_yprev"):
+        return False
+    return bool(_lib.load().tt_gru_yprev_supported(dtype_code(cfg.dtype), 2 * cfg.ntowers, B, T, H, 6 * H, 2 * H))
+
+
+def _gru_layer_fwd(cfg, xs, K, ldx, packs, layer, B, T, seeds, want_x1, ws, yprev=False, want_final=False):
     """Input projection + one bidirectional GRU layer for every tower. The dropout copy
     X1 (want_x1) draws keep(seed, rank*B*T + b*T + t, col): on N data-parallel ranks the
-    masks are those the single-process run of the global batch draws."""
+    masks are those the single-process run of the global batch draws.
+    yprev: Y is stored in the previous-state layout (row t holds the state the step at t
+    starts from, zeros at a direction's first step) and, with want_final, the final states
+    cat(h_fwd at T-1, h_rev at 0) [B, 2H] per tower come back as the fourth result."""
     n, H, dt, dev = cfg.ntowers, cfg.H, cfg.dtype, xs[0].device
     BT = B * T
     G = [_alloc((BT, 6 * H), dt, dev) for _ in range(n)]
@@ -352,12 +367,20 @@ def _gru_layer_fwd(cfg, xs, K, ldx, packs, layer, B, T, seeds, want_x1, ws):
         kname = "gru_fwd_seq<"
     else:
         kname = "gru_fwd_step<"
+    hfin = [_alloc((B, 2 * H), dt, dev) for _ in range(n)] if yprev and want_final else None
     with timing.region("gru_fwd", nl, 2.0 * B * H * 3 * H * 2 * n * (T - 1), float(B * T * H * 2 * n * per),
                        kernel=kname):
-        call("tt_gru_fwd", dtype_code(dt), recs, 2 * n, B, T, H, 6 * H, 2 * H, cfg.drop_p if want_x1 else 0.0,
-             ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream_ptr(dev))
+        if yprev:
+            fin = None
+            if hfin is not None:
+                fin = (ctypes.c_void_p * (2 * n))(*[hfin[ti][:, d * H:].data_ptr() for ti in range(n) for d in range(2)])
+            call("tt_gru_fwd_yprev", dtype_code(dt), recs, fin, 2 * n, B, T, H, 6 * H, 2 * H, 2 * H,
+                 cfg.drop_p if want_x1 else 0.0, ws.data_ptr(), ws.numel(), stream_ptr(dev))
+        else:
+            call("tt_gru_fwd", dtype_code(dt), recs, 2 * n, B, T, H, 6 * H, 2 * H, cfg.drop_p if want_x1 else 0.0,
+                 ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream_ptr(dev))
     del G
-    return Y, X1, S
+    return Y, X1, S, hfin
 
 
 def _gru_layer_infer(cfg, xs, K, ldx, packs, layer, B, T, ws, final_only):
@@ -458,8 +481,9 @@ def towers_infer(cfg: TowerCfg, table, xs, params):
         return tuple(outs)
 
 
-def _gru_layer_bwd(cfg, layer, B, T, S, Y, dY, dfinal, packs):
-    """Returns dG ([B*T, 8H] per tower: dL/dg_x of both directions in columns [0, 6H),
+def _gru_layer_bwd(cfg, layer, B, T, S, Y, dY, dfinal, packs, yprev=False):
+    """yprev: Y is in the previous-state layout (tt_gru_bwd_yprev).
+    Returns dG ([B*T, 8H] per tower: dL/dg_x of both directions in columns [0, 6H),
     dL/d(W_hn h) of both directions in [6H, 8H); dL/dg_h = [r|z of dL/dg_x, W_hn block])
     and bias grads (dbih, dbhh per tower/dir)."""
     n, H, dt, dev = cfg.ntowers, cfg.H, cfg.dtype, Y[0].device
@@ -495,7 +519,8 @@ def _gru_layer_bwd(cfg, layer, B, T, S, Y, dY, dfinal, packs):
              "gru_bwd_big" if dt == torch.bfloat16 and H % 256 == 0 and _lib.get_option("gru_bwd_big") else "gru_bwd_step<")
     with timing.region("gru_bwd", nl, 2.0 * B * 3 * H * H * 2 * n * (T - 1), float(B * T * H * 2 * n * per),
                        kernel=kname):
-        call("tt_gru_bwd", dtype_code(dt), recs, 2 * n, B, T, H, 2 * H, 8 * H, ldf, stream_ptr(dev))
+        call("tt_gru_bwd_yprev" if yprev else "tt_gru_bwd", dtype_code(dt), recs, 2 * n, B, T, H, 2 * H, 8 * H, ldf,
+             stream_ptr(dev))
     sums = _alloc((n * 2, 4 * H), torch.float32, dev)
     for i in range(2 * n):
         ops.colsum(part[i], nbr, 4 * H, 4 * H, sums[i])
@@ -521,8 +546,10 @@ def _wgrad_stream(dev) -> torch.cuda.Stream:
     return s
 
 
-def _weight_grads(cfg, B, T, dG, Xin, K, ldx, Y, kr=None):
-    """dW_ih = dG^T Xin, dW_hh = dGH^T Y_{t-1} for all (tower, dir) in two batched TN GEMMs."""
+def _weight_grads(cfg, B, T, dG, Xin, K, ldx, Y, kr=None, yprev=False):
+    """dW_ih = dG^T Xin, dW_hh = dGH^T Y_{t-1} for all (tower, dir) in two batched TN GEMMs.
+    yprev: Y already holds h_{t-1} at row t (zeros at a direction's first step), so dW_hh is a
+    plain TN product like dW_ih; otherwise its B operand is read time-shifted (bshift)."""
     n, H, dt, dev = cfg.ntowers, cfg.H, cfg.dtype, dG[0].device
     BT = B * T
     dWih = [[_alloc((3 * H, K), torch.float32, dev) for _ in range(2)] for _ in range(n)]
@@ -562,8 +589,12 @@ def _weight_grads(cfg, B, T, dG, Xin, K, ldx, Y, kr=None):
                      b_kouter=True, dtype=dt, out_dtype=torch.float32)
     with timing.region("wgrad_hh", 1, 2.0 * 3 * H * H * BT * 2 * n,
                        float(n * (esz * BT * (6 * H + 2 * H) + 2 * 3 * H * H * 4))):
-        ops.gemm(a_hh, b_hh, c_hh, m=3 * H, n=H, k=BT, lda=8 * H, ldb=2 * H, ldc=H, a_kouter=True, b_kouter=True,
-                 dtype=dt, out_dtype=torch.float32, bshift=sh, seq_t=T, a_hi=a_hi, a_split=2 * H)
+        if yprev:
+            ops.gemm(a_hh, b_hh, c_hh, m=3 * H, n=H, k=BT, lda=8 * H, ldb=2 * H, ldc=H, a_kouter=True, b_kouter=True,
+                     dtype=dt, out_dtype=torch.float32, a_hi=a_hi, a_split=2 * H)
+        else:
+            ops.gemm(a_hh, b_hh, c_hh, m=3 * H, n=H, k=BT, lda=8 * H, ldb=2 * H, ldc=H, a_kouter=True, b_kouter=True,
+                     dtype=dt, out_dtype=torch.float32, bshift=sh, seq_t=T, a_hi=a_hi, a_split=2 * H)
     return dWih, dWhh
 
 
@@ -593,18 +624,29 @@ class TowersFn(torch.autograd.Function):
         seeds = [int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) for _ in range(n)] if train_drop else [0] * n
         # one workspace for both layers (same shape; the launches are stream-ordered)
         ws = gru_fwd_workspace(2 * n, B, T, H, dt, dev)
-        Y0, X1, S0 = _gru_layer_fwd(cfg, X0, Ep, Ep, packs, 0, B, T, seeds, train_drop, ws)
+        # Previous-state layout of the layer outputs (option gru_yprev, where the library has
+        # it for this shape): layer 1's Y is read only by the BPTT, dW_hh and the head, all of
+        # which want h_{t-1} or the final state; layer 0's Y also feeds layer 1 at its own time
+        # index unless the dropout copy X1 does, so it needs train_drop.
+        yp1 = ws is not None and yprev_supported(cfg, B, T)
+        yp0 = yp1 and train_drop
+        Y0, X1, S0, _ = _gru_layer_fwd(cfg, X0, Ep, Ep, packs, 0, B, T, seeds, train_drop, ws, yprev=yp0)
         Xl1 = X1 if train_drop else Y0
-        Y1, _, S1 = _gru_layer_fwd(cfg, Xl1, 2 * H, 2 * H, packs, 1, B, T, seeds, False, ws)
+        Y1, _, S1, hfin = _gru_layer_fwd(cfg, Xl1, 2 * H, 2 * H, packs, 1, B, T, seeds, False, ws, yprev=yp1,
+                                         want_final=True)
         if ws is not None:
             # only a forward that records autograd state arms the optimiser's step guard
             watch_gru_status(ws, arm=any(ctx.needs_input_grad))
         # cat(h_fwd at t=T-1, h_rev at t=0) -> [B, 2H] (enhanced_two_tower.py:53,59)
         hcat = []
         for ti in range(n):
+            if hfin is not None:  # written by the kernel
+                hcat.append(hfin[ti].to(HEAD_DT))
+                continue
             y = Y1[ti].view(B, T, 2 * H)
             hcat.append(torch.cat([y[:, T - 1, :H], y[:, 0, H:]], 1).to(HEAD_DT).contiguous())
         ctx.cfg = cfg
+        ctx.yprev = (yp0, yp1)
         ctx.group = group
         ctx.params = params
         ctx.dims = (B, T, Ep)
@@ -638,6 +680,7 @@ class TowersFn(torch.autograd.Function):
         check_gru_status(wait=False)  # the forwards that have finished by now
         n, dt, E, H, h = cfg.ntowers, cfg.dtype, cfg.E, cfg.H, cfg.h
         B, T, Ep = ctx.dims
+        yp0, yp1 = ctx.yprev
         packs = ctx.packs
         X0, Y0, X1, S0, Y1, S1, hcat, p1s, means, rstds, us = ctx.acts
         dev = Y0[0].device
@@ -677,13 +720,13 @@ class TowersFn(torch.autograd.Function):
             head_grads[ti] = [dw1, db1, dg, dbeta, dw2, db2]
             dhcat.append(dx)
         # ---- GRU layer 1: dfinal enters at the last processed step of each direction
-        dG1, dbih1, dbhh1 = _gru_layer_bwd(cfg, 1, B, T, S1, Y1, None, dhcat, packs)
+        dG1, dbih1, dbhh1 = _gru_layer_bwd(cfg, 1, B, T, S1, Y1, None, dhcat, packs, yprev=yp1)
         Xl1 = X1 if X1 is not None else Y0
         red = dist.OverlapReducer(ctx.group[0]) if ctx.group is not None else None
         gl = [{} for _ in range(n)]
 
         def layer1_wgrads():
-            dWih1, dWhh1 = _weight_grads(cfg, B, T, dG1, Xl1, 2 * H, 2 * H, Y1)
+            dWih1, dWhh1 = _weight_grads(cfg, B, T, dG1, Xl1, 2 * H, 2 * H, Y1, yprev=yp1)
             _layer_grads(gl, 1, E, Ep, dWih1, dWhh1, dbih1, dbhh1)
             # data-parallel: the head + layer-1 gradients are summed across ranks while the
             # layer-0 BPTT below runs (dist.OverlapReducer)
@@ -719,9 +762,9 @@ class TowersFn(torch.autograd.Function):
                 layer1_wgrads()
         del dG1
         # ---- GRU layer 0
-        dG0, dbih0, dbhh0 = _gru_layer_bwd(cfg, 0, B, T, S0, Y0, dY0, None, packs)
+        dG0, dbih0, dbhh0 = _gru_layer_bwd(cfg, 0, B, T, S0, Y0, dY0, None, packs, yprev=yp0)
         del dY0
-        dWih0, dWhh0 = _weight_grads(cfg, B, T, dG0, X0, Ep, Ep, Y0, kr=E)
+        dWih0, dWhh0 = _weight_grads(cfg, B, T, dG0, X0, Ep, Ep, Y0, kr=E, yprev=yp0)
         gl0 = [{} for _ in range(n)]
         _layer_grads(gl0, 0, E, Ep, dWih0, dWhh0, dbih0, dbhh0)
         if side is not None:

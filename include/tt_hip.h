@@ -367,6 +367,31 @@ int tt_infonce_bwd(int dtype, const void* qn, long bq, const void* dn, long nd, 
                    const float* gscale, float* dqn, float* ddn, void* ws, void* stream);
 long tt_infonce_bwd_ws_size(int dtype, long bq, long nd, int h);
 
+/* Symmetric InfoNCE (simple_two_tower.py:73-78): (CE(S, arange) + CE(S^T, arange)) / 2 over
+ * the square S = inv_tau * qn dn^T, qn and dn [n, h]; the label of row i is column i and
+ * there is no off-diagonal shift. dtype and alignment as tt_infonce_fwd; n = 0 is a no-op.
+ * Forward: one pass over the score tiles gives both directions: the running row
+ * (max, sum-exp) of tt_infonce_fwd and, per 128-column tile, the (max, sum-exp) of each
+ * column over the workgroup's 128 rows, written as one partial per (row block, column)
+ * and merged in ascending block order. Outputs lse_row[i] = LSE_j S_ij, lse_col[i] =
+ * LSE_j S_ji and row_loss[i] = ((lse_row[i] - S_ii) + (lse_col[i] - S_ii)) / 2.
+ * Deterministic: no float atomics, nothing depends on the previous contents of ws
+ * (tt_infonce_sym_fwd_ws_size(n, h) bytes). */
+int tt_infonce_sym_fwd(int dtype, const void* qn, const void* dn, long n, int h, float inv_tau,
+                       float* lse_row, float* lse_col, float* row_loss, void* ws, void* stream);
+long tt_infonce_sym_fwd_ws_size(long n, int h);
+/* Gradient of g * sum_i row_loss[i]: with
+ *   dS_ij = g/2 * (exp(S_ij - lse_row[i]) + exp(S_ij - lse_col[j]) - 2 [i == j]),
+ * dqn = inv_tau dS dn and ddn = inv_tau dS^T qn (fp32 [n, h], overwritten). bf16 with h in
+ * {128, 256} recomputes the score tiles and never writes dS (the fused backward of
+ * tt_infonce_bwd, both LSE vectors read by both roles); every other case, and option
+ * infonce_flash = 0, writes dS in dtype and takes two tt_gemm products. gscale as
+ * tt_infonce_bwd. ws: tt_infonce_sym_bwd_ws_size bytes. */
+int tt_infonce_sym_bwd(int dtype, const void* qn, const void* dn, long n, int h, float inv_tau,
+                       const float* lse_row, const float* lse_col, const float* gscale,
+                       float* dqn, float* ddn, void* ws, void* stream);
+long tt_infonce_sym_bwd_ws_size(int dtype, long n, int h);
+
 /* Hard-negative mining, batched over rows (get_hard_negatives,
  * enhanced_two_tower.py:123-133): sims = qn dn^T (cosine for normalised inputs), the
  * positive column label_offset+i set to -1 (label_offset < 0: no column masked), top-k
@@ -448,6 +473,26 @@ int tt_sum(const float* x, long n, float scale, float* out, void* stream);
 int tt_adam_multi(float* const* params, const float* const* grads, float* const* exp_avg,
                   float* const* exp_avg_sq, const long* sizes, int ntensors, float lr, float beta1,
                   float beta2, float eps, float weight_decay, int step, const int32_t* skip, void* stream);
+/* torch.optim.AdamW (simple_two_tower.py:193), same parameters: decoupled decay in the
+ * order of torch's single-tensor AdamW, p *= (float)(1 - (double)lr * weight_decay) first,
+ * then the Adam update above with g untouched. skip as tt_adam_multi. */
+int tt_adamw_multi(float* const* params, const float* const* grads, float* const* exp_avg,
+                   float* const* exp_avg_sq, const long* sizes, int ntensors, float lr, float beta1,
+                   float beta2, float eps, float weight_decay, int step, const int32_t* skip, void* stream);
+
+/* sumsq[0] = (accumulate ? sumsq[0] : 0) + sum of g^2 over up to 48 fp32 tensors (device
+ * scalar); more tensors chain through accumulate. One fp32 partial per 4096-element chunk
+ * of the concatenated tensors, then one workgroup adds the partials in a fixed order:
+ * the same inputs give the same bits. ws: tt_grad_norm_ws_size(sizes, ntensors) bytes. */
+int tt_grad_norm_multi(const float* const* grads, const long* sizes, int ntensors, int accumulate,
+                       float* sumsq, void* ws, void* stream);
+long tt_grad_norm_ws_size(const long* sizes, int ntensors);
+/* torch.nn.utils.clip_grad_norm_ (simple_two_tower.py:239), every value computed on the
+ * device: total = sqrt(sumsq[0]), coef = min(1, max_norm / (total + 1e-6)), g *= coef for
+ * up to 48 tensors; total_norm_out[0] = total (optional). A non-finite norm propagates
+ * into the gradients as with error_if_nonfinite=False. */
+int tt_clip_scale_multi(float* const* grads, const long* sizes, int ntensors, const float* sumsq,
+                        float max_norm, float* total_norm_out, void* stream);
 
 #ifdef __cplusplus
 }

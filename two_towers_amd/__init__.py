@@ -9,9 +9,11 @@ of enhanced_two_tower.py (and the margin family of margin_two_tower.py in .margi
 from .data import (EnhancedDataset, EnhancedIdDataset, MSMarcoDataset, Vocab, encode_batch, encode_ids,
                    load_ms_marco_train, load_word2vec, pairs_from_msmarco)
 from .margin import MarginIdDataset, SimpleDataset, TwoTowerModel, margin_ids
-from .losses import HardNegativeMarginLoss, InfoNCELoss, MarginRankingLoss, get_hard_negatives, mine_hard_negatives
+from .losses import (HardNegativeMarginLoss, InfoNCELoss, MarginRankingLoss, SymmetricInfoNCELoss,
+                     get_hard_negatives, mine_hard_negatives)
 from .model import EnhancedTwoTower, EnhancedTwoTowerModel
-from .optim import Adam
+from .optim import Adam, AdamW, clip_grad_norm_
+from .simple import SimpleTwoTower
 from ._lib import GruTimeoutError
 from .towers import check_gru_status
 
@@ -20,5 +22,6 @@ __all__ = [
     "get_hard_negatives", "mine_hard_negatives", "EnhancedDataset", "EnhancedIdDataset", "MSMarcoDataset",
     "Vocab", "encode_ids", "encode_batch", "load_word2vec", "load_ms_marco_train", "pairs_from_msmarco", "Adam",
     "TwoTowerModel", "SimpleDataset", "MarginIdDataset", "margin_ids", "check_gru_status", "GruTimeoutError",
+    "SimpleTwoTower", "SymmetricInfoNCELoss", "AdamW", "clip_grad_norm_",
 ]
 __version__ = "0.1.0"

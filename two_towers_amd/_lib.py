@@ -165,6 +165,12 @@ _SIGS = {
     "tt_infonce_bwd": (c_int, [c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_float, c_float, c_long,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tt_infonce_bwd_ws_size": (c_long, [c_int, c_long, c_long, c_int]),
+    "tt_infonce_sym_fwd": (c_int, [c_int, c_void_p, c_void_p, c_long, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
+    "tt_infonce_sym_fwd_ws_size": (c_long, [c_long, c_int]),
+    "tt_infonce_sym_bwd": (c_int, [c_int, c_void_p, c_void_p, c_long, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tt_infonce_sym_bwd_ws_size": (c_long, [c_int, c_long, c_int]),
     "tt_hardneg_topk": (c_int, [c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_long, c_int, c_void_p,
                                 c_void_p, c_void_p, c_void_p]),
     "tt_hardneg_ws_size": (c_long, [c_int, c_long, c_long, c_int, c_int]),
@@ -184,6 +190,13 @@ _SIGS = {
     "tt_adam_multi": (c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
                               POINTER(c_long), c_int, c_float, c_float, c_float, c_float, c_float, c_int,
                               c_void_p, c_void_p]),
+    "tt_adamw_multi": (c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                               POINTER(c_long), c_int, c_float, c_float, c_float, c_float, c_float, c_int,
+                               c_void_p, c_void_p]),
+    "tt_grad_norm_multi": (c_int, [POINTER(c_void_p), POINTER(c_long), c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "tt_grad_norm_ws_size": (c_long, [POINTER(c_long), c_int]),
+    "tt_clip_scale_multi": (c_int, [POINTER(c_void_p), POINTER(c_long), c_int, c_void_p, c_float, c_void_p,
+                                    c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -171,15 +171,179 @@ __global__ __launch_bounds__(256) void infonce_finalize_kernel(const float* __re
   row_loss[row] = v - diag[row];
 }
 
+// ------------------------------------------------------- symmetric InfoNCE fwd
+// Both directions of (CE(S, arange) + CE(S^T, arange)) / 2 from one pass over the score
+// tiles of the square problem S = inv_tau qn dn^T [n, n]. Grid and row direction as
+// infonce_fwd_kernel. Column direction: per 128-column tile the (max, sum-exp) over the
+// workgroup's 128 rows: the 16 row values a lane holds for a column, then the four
+// lane>>4 groups, then the two waves that share wn (LDS, double-buffered by tile parity:
+// one barrier per tile). One partial per (row block, column) goes to cpm/cpl [rb][n]; each
+// is written by exactly one workgroup, and infonce_sym_finalize_kernel merges them in
+// ascending block order. Rows >= n never enter a column's sum, columns >= n never a row's.
+template <typename T>
+__global__ __launch_bounds__(256) void infonce_sym_fwd_kernel(const T* __restrict__ qn, const T* __restrict__ dn,
+                                                              long n, int h, float inv_tau, int ct_per_split,
+                                                              float* __restrict__ pm, float* __restrict__ pl,
+                                                              float* __restrict__ cpm, float* __restrict__ cpl,
+                                                              float* __restrict__ diag) {
+  using ML = ttg::MainLoop<T, false, false, 128, 128>;
+  __shared__ __attribute__((aligned(16))) char lds[ML::LDS_BYTES];
+  __shared__ float red_m[2][128], red_l[2][128];
+  __shared__ float col_m[2][2][128], col_l[2][2][128];  // [tile parity][wave >> 1][column]
+  const int m0 = blockIdx.y * 128;
+  const long nct = (n + 127) / 128;
+  const long ct0 = (long)blockIdx.x * ct_per_split;
+  const long ct1 = std::min(nct, ct0 + ct_per_split);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
+  const int nk = (h * (int)sizeof(T) + ttg::KTB - 1) / ttg::KTB;
+  float rm[4][4], rl[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { rm[i][r] = -FLT_MAX; rl[i][r] = 0.f; }
+
+  for (long ct = ct0; ct < ct1; ++ct) {
+    const int n0 = (int)(ct * 128);
+    const int par = (int)((ct - ct0) & 1);
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    ML::run(ttg::KCPlain<T>{qn, h, m0, (int)n}, ttg::KCPlain<T>{dn, h, n0, (int)n}, h, 0, nk, lds, acc);
+    float cm[4], cl[4];  // per column j of this lane: over the 16 rows it holds
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float t = -FLT_MAX;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const long row = m0 + wm + 16 * i + 4 * (lane >> 4) + r;
+          if (row < n) t = fmaxf(t, acc[i][j][r] * inv_tau);
+        }
+      cm[j] = t;
+      cl[j] = 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const long row = m0 + wm + 16 * i + 4 * (lane >> 4) + r;
+        float sv[4];
+        float tmax = -FLT_MAX;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const long col = n0 + wn + 16 * j + (lane & 15);
+          float s = acc[i][j][r] * inv_tau;
+          if (col == row && row < n) diag[row] = s;
+          if (row < n) cl[j] += __expf(s - cm[j]);
+          if (col >= n) s = -FLT_MAX;
+          sv[j] = s;
+          tmax = fmaxf(tmax, s);
+        }
+        const float nm = fmaxf(rm[i][r], tmax);
+        float l = rl[i][r] * __expf(rm[i][r] - nm);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) l += (sv[j] > -FLT_MAX) ? __expf(sv[j] - nm) : 0.f;
+        rm[i][r] = nm;
+        rl[i][r] = l;
+      }
+    // columns: the four lane>>4 groups of the wave, then the wave with the same wn
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float M = cm[j], L = cl[j];
+#pragma unroll
+      for (int o = 16; o <= 32; o <<= 1) {
+        const float Mo = __shfl_xor(M, o, 64), Lo = __shfl_xor(L, o, 64);
+        const float Mn = fmaxf(M, Mo);
+        L = L * __expf(M - Mn) + Lo * __expf(Mo - Mn);
+        M = Mn;
+      }
+      if (lane < 16) {
+        col_m[par][wave >> 1][wn + 16 * j + lane] = M;
+        col_l[par][wave >> 1][wn + 16 * j + lane] = L;
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < 128) {
+      const long col = (long)n0 + threadIdx.x;
+      if (col < n) {
+        const float a = col_m[par][0][threadIdx.x], b = col_m[par][1][threadIdx.x];
+        const float M = fmaxf(a, b);
+        const float L = col_l[par][0][threadIdx.x] * __expf(a - M) + col_l[par][1][threadIdx.x] * __expf(b - M);
+        cpm[(long)blockIdx.y * n + col] = M;
+        cpl[(long)blockIdx.y * n + col] = L;
+      }
+    }
+  }
+  // rows: merge the 16 lanes sharing each row, then the two waves sharing it
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float M = max16(rm[i][r]);
+      const float L = sum16(rl[i][r] * __expf(rm[i][r] - M));
+      if ((lane & 15) == 0) {
+        const int rr = wm + 16 * i + 4 * (lane >> 4) + r;
+        red_m[wave & 1][rr] = M;
+        red_l[wave & 1][rr] = L;
+      }
+    }
+  __syncthreads();
+  if (threadIdx.x < 128) {
+    const long row = m0 + threadIdx.x;
+    if (row < n) {
+      const float a = red_m[0][threadIdx.x], b = red_m[1][threadIdx.x];
+      const float M = fmaxf(a, b);
+      const float L = red_l[0][threadIdx.x] * __expf(a - M) + red_l[1][threadIdx.x] * __expf(b - M);
+      pm[(long)blockIdx.x * n + row] = M;
+      pl[(long)blockIdx.x * n + row] = L;
+    }
+  }
+}
+
+// index i: its row LSE from the column-split partials, its column LSE from the row-block
+// partials (ascending block order), row_loss = ((lse_row - S_ii) + (lse_col - S_ii)) / 2
+__global__ __launch_bounds__(256) void infonce_sym_finalize_kernel(const float* __restrict__ pm,
+                                                                   const float* __restrict__ pl, int splits,
+                                                                   const float* __restrict__ cpm,
+                                                                   const float* __restrict__ cpl, int rb, long n,
+                                                                   const float* __restrict__ diag,
+                                                                   float* __restrict__ lse_row,
+                                                                   float* __restrict__ lse_col,
+                                                                   float* __restrict__ row_loss) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  float M = -FLT_MAX;
+  for (int s = 0; s < splits; ++s) M = fmaxf(M, pm[(long)s * n + i]);
+  float L = 0.f;
+  for (int s = 0; s < splits; ++s) L += pl[(long)s * n + i] * __expf(pm[(long)s * n + i] - M);
+  const float lr = M + __logf(L);
+  M = -FLT_MAX;
+  for (int b = 0; b < rb; ++b) M = fmaxf(M, cpm[(long)b * n + i]);
+  L = 0.f;
+  for (int b = 0; b < rb; ++b) L += cpl[(long)b * n + i] * __expf(cpm[(long)b * n + i] - M);
+  const float lc = M + __logf(L);
+  lse_row[i] = lr;
+  lse_col[i] = lc;
+  const float d = diag[i];
+  row_loss[i] = 0.5f * ((lr - d) + (lc - d));
+}
+
 // dS[i][j] = g * (softmax_ij - [j == label_i]) in dtype, full tiles; g = *gscale (the
 // upstream gradient, read on the device: no host sync) or 1 when gscale is null.
-template <typename T>
+// SYM (square, label_off 0, no offdiag): lse is the row LSE, lse_col the column LSE and
+// dS[i][j] = g/2 * (exp(s - lse[i]) + exp(s - lse_col[j]) - 2 [i == j]).
+template <typename T, bool SYM = false>
 __global__ __launch_bounds__(256) void infonce_dscore_kernel(const T* __restrict__ qn, long bq,
                                                              const T* __restrict__ dn, long nd, int h, float inv_tau,
                                                              float offdiag, long label_off,
                                                              const float* __restrict__ lse,
                                                              const float* __restrict__ gscale, long ldds,
-                                                             T* __restrict__ ds) {
+                                                             T* __restrict__ ds,
+                                                             const float* __restrict__ lse_col) {
   const float gs = gscale ? *gscale : 1.f;
   using ML = ttg::MainLoop<T, false, false, 128, 128>;
   __shared__ __attribute__((aligned(16))) char lds[ML::LDS_BYTES];
@@ -196,9 +360,14 @@ __global__ __launch_bounds__(256) void infonce_dscore_kernel(const T* __restrict
     if (row >= bq || col >= nd) return;
     const bool lab = (col == label_off + row);
     float s = v * inv_tau;
-    if (!lab) s -= offdiag;
-    const float p = __expf(s - lse[row]);
-    Elt<T>::st(ds + row * ldds + col, gs * (p - (lab ? 1.f : 0.f)));
+    if constexpr (SYM) {
+      const float p = __expf(s - lse[row]) + __expf(s - lse_col[col]);
+      Elt<T>::st(ds + row * ldds + col, 0.5f * gs * (p - (lab ? 2.f : 0.f)));
+    } else {
+      if (!lab) s -= offdiag;
+      const float p = __expf(s - lse[row]);
+      Elt<T>::st(ds + row * ldds + col, gs * (p - (lab ? 1.f : 0.f)));
+    }
   });
 }
 
@@ -263,13 +432,14 @@ TT_DEV void flash_stage(const bf16_t* src, long rows, long r0, int nrows_img, ui
     }
 }
 
-template <int H, bool OWNQ>
+template <int H, bool OWNQ, bool SYM = false>
 __global__ __launch_bounds__(512) void infonce_bwd_flash_kernel(const bf16_t* __restrict__ qn, long bq,
                                                                 const bf16_t* __restrict__ dn, long nd, float inv_tau,
                                                                 float offdiag, long label_off,
                                                                 const float* __restrict__ lse,
                                                                 const float* __restrict__ gscale, int tiles_per_split,
-                                                                float* __restrict__ out) {
+                                                                float* __restrict__ out,
+                                                                const float* __restrict__ lse_col) {
   using C = FlashCfg<H>;
   __shared__ __attribute__((aligned(16))) char lds[C::LDS];
   const float gs = gscale ? *gscale : 1.f;
@@ -289,14 +459,18 @@ __global__ __launch_bounds__(512) void infonce_bwd_flash_kernel(const bf16_t* __
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int j = 0; j < C::NO; ++j) acc_o[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // per own row (product-1 layout: rows wm + 16i + 4(lane>>4) + r): its lse when OWNQ
+  // per own row (product-1 layout: rows wm + 16i + 4(lane>>4) + r): its lse when OWNQ.
+  // SYM: both roles read both LSE vectors: the own rows' here (row LSE when OWNQ, column
+  // LSE otherwise), the swept tile's into lx below (the other vector)
+  const float* lse_own = SYM ? (OWNQ ? lse : lse_col) : lse;
+  const float* lse_x = SYM ? (OWNQ ? lse_col : lse) : lse;
   float lown[2][4];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const long row = o0 + wm + 16 * i + 4 * (lane >> 4) + r;
-      lown[i][r] = (OWNQ && row < nown) ? lse[row] : 0.f;
+      lown[i][r] = ((OWNQ || SYM) && row < nown) ? lse_own[row] : 0.f;
     }
   if (t0 < t1) {
     flash_stage<H>(O, nown, o0, 128, lb);
@@ -330,11 +504,11 @@ __global__ __launch_bounds__(512) void infonce_bwd_flash_kernel(const bf16_t* __
       }
     // dS (own row, tile row) -> bf16 K-contig image [128 own rows][64 tile rows]
     float lx[2] = {0.f, 0.f};
-    if (!OWNQ) {
+    if (!OWNQ || SYM) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const long xr = t * 64 + wn + 16 * j + (lane & 15);
-        lx[j] = xr < nx ? lse[xr] : 0.f;
+        lx[j] = xr < nx ? lse_x[xr] : 0.f;
       }
     }
 #pragma unroll
@@ -348,9 +522,15 @@ __global__ __launch_bounds__(512) void infonce_bwd_flash_kernel(const bf16_t* __
           const long qi = OWNQ ? orow : xrow, dj = OWNQ ? xrow : orow;
           const bool lab = dj == label_off + qi;
           float s = acc_s[i][j][r] * inv_tau;
-          if (!lab) s -= offdiag;
-          const float p = __expf(s - (OWNQ ? lown[i][r] : lx[j]));
-          const float v = (orow < nown && xrow < nx) ? gs * (p - (lab ? 1.f : 0.f)) : 0.f;
+          float v;
+          if constexpr (SYM) {  // g/2 (exp(s - lse_row_i) + exp(s - lse_col_j) - 2 [i == j])
+            const float p = __expf(s - lown[i][r]) + __expf(s - lx[j]);
+            v = (orow < nown && xrow < nx) ? 0.5f * gs * (p - (lab ? 2.f : 0.f)) : 0.f;
+          } else {
+            if (!lab) s -= offdiag;
+            const float p = __expf(s - (OWNQ ? lown[i][r] : lx[j]));
+            v = (orow < nown && xrow < nx) ? gs * (p - (lab ? 1.f : 0.f)) : 0.f;
+          }
           *reinterpret_cast<bf16_t*>(dsimg + orl * 128 + ((((xcl >> 3) ^ ((orl >> 1) & 7))) << 4) + (xcl & 7) * 2) =
               f2bf(v);
         }
@@ -748,24 +928,66 @@ extern "C" long tt_infonce_bwd_ws_size(int dtype, long bq, long nd, int h) {
 }
 
 // one role of the fused backward: out = dq (OWNQ) or dd, through slabs when split
-template <int H, bool OWNQ>
+template <int H, bool OWNQ, bool SYM = false>
 static int flash_role(const bf16_t* qn, long bq, const bf16_t* dn, long nd, float inv_tau, float offdiag,
                       long label_off, const float* lse, const float* gscale, float* out, float* slab,
-                      hipStream_t st) {
+                      hipStream_t st, const float* lse_col = nullptr) {
   const long nown = OWNQ ? bq : nd, nx = OWNQ ? nd : bq;
   const long ntile = (nx + 63) / 64;
   int splits = flash_splits(nown, nx);
   const int per = tt_ceil_div(ntile, splits);
   splits = tt_ceil_div(ntile, per);
   const dim3 grid((unsigned)splits, (unsigned)tt_ceil_div(nown, 128));
-  hipLaunchKernelGGL((infonce_bwd_flash_kernel<H, OWNQ>), grid, dim3(512), 0, st, qn, bq, dn, nd, inv_tau, offdiag,
-                     label_off, lse, gscale, per, splits > 1 ? slab : out);
+  hipLaunchKernelGGL((infonce_bwd_flash_kernel<H, OWNQ, SYM>), grid, dim3(512), 0, st, qn, bq, dn, nd, inv_tau,
+                     offdiag, label_off, lse, gscale, per, splits > 1 ? slab : out, lse_col);
   TT_CHECK_LAUNCH("infonce_bwd_flash_kernel");
   if (splits > 1) {
     const long n = nown * H;
     hipLaunchKernelGGL(infonce_slab_sum_kernel, dim3((unsigned)tt_ceil_div(n / 4, 256)), dim3(256), 0, st, slab,
                        splits, n, out);
     TT_CHECK_LAUNCH("infonce_slab_sum_kernel");
+  }
+  return 0;
+}
+
+// the materialised backward: dS in dtype through infonce_dscore_kernel, then two tt_gemm
+// products (SYM: the symmetric dS, lse = row LSE, lse_col = column LSE)
+template <bool SYM>
+static int infonce_bwd_materialised(int dtype, const void* qn, long bq, const void* dn, long nd, int h, float inv_tau,
+                                    float offdiag_sub, long label_offset, const float* lse, const float* lse_col,
+                                    const float* gscale, float* dqn, float* ddn, void* ws, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  InfoWs w;
+  infonce_ws(dtype, bq, nd, h, &w);
+  char* base = static_cast<char*>(ws);
+  void* ds = base + w.ds;
+  float* sk = reinterpret_cast<float*>(base + w.sk);
+  const long ldds = (nd + 7) / 8 * 8;  // 16-byte aligned rows for the dS operand
+  dim3 grid((unsigned)tt_ceil_div(nd, 128), (unsigned)tt_ceil_div(bq, 128));
+  if (dtype == TT_DT_BF16)
+    hipLaunchKernelGGL((infonce_dscore_kernel<bf16_t, SYM>), grid, dim3(256), 0, st, (const bf16_t*)qn, bq,
+                       (const bf16_t*)dn, nd, h, inv_tau, offdiag_sub, label_offset, lse, gscale, ldds, (bf16_t*)ds,
+                       lse_col);
+  else
+    hipLaunchKernelGGL((infonce_dscore_kernel<float, SYM>), grid, dim3(256), 0, st, (const float*)qn, bq,
+                       (const float*)dn, nd, h, inv_tau, offdiag_sub, label_offset, lse, gscale, ldds, (float*)ds,
+                       lse_col);
+  TT_CHECK_LAUNCH("infonce_dscore_kernel");
+  // dqn = inv_tau * dS dn   (NN)
+  {
+    tt_gemm_batch g{};
+    g.a[0] = ds; g.b[0] = dn; g.c[0] = dqn;
+    const int sp = tt_gemm_pick_splits((int)bq, h, (int)nd, 1);
+    TT_PROPAGATE(tt_gemm(dtype, TT_DT_F32, 0, 1, (int)bq, h, (int)nd, &g, 1, ldds, h, h, inv_tau, 0, 0, 0, 0, 0.f, sp,
+                         sk, stream));
+  }
+  // ddn = inv_tau * dS^T qn (TN)
+  {
+    tt_gemm_batch g{};
+    g.a[0] = ds; g.b[0] = qn; g.c[0] = ddn;
+    const int sp = tt_gemm_pick_splits((int)nd, h, (int)bq, 1);
+    TT_PROPAGATE(tt_gemm(dtype, TT_DT_F32, 1, 1, (int)nd, h, (int)bq, &g, 1, ldds, h, h, inv_tau, 0, 0, 0, 0, 0.f, sp,
+                         sk, stream));
   }
   return 0;
 }
@@ -792,37 +1014,92 @@ extern "C" int tt_infonce_bwd(int dtype, const void* qn, long bq, const void* dn
     }
     return 0;
   }
-  InfoWs w;
-  infonce_ws(dtype, bq, nd, h, &w);
-  char* base = static_cast<char*>(ws);
-  void* ds = base + w.ds;
-  float* sk = reinterpret_cast<float*>(base + w.sk);
-  const long ldds = (nd + 7) / 8 * 8;  // 16-byte aligned rows for the dS operand
-  dim3 grid((unsigned)tt_ceil_div(nd, 128), (unsigned)tt_ceil_div(bq, 128));
+  return infonce_bwd_materialised<false>(dtype, qn, bq, dn, nd, h, inv_tau, offdiag_sub, label_offset, lse, nullptr,
+                                         gscale, dqn, ddn, ws, stream);
+}
+
+// ------------------------------------------------------------ symmetric InfoNCE
+namespace {
+struct SymFwdPlan {
+  int rb, splits, per;
+};
+inline SymFwdPlan sym_fwd_plan(long n) {
+  SymFwdPlan p{};
+  p.rb = tt_ceil_div(n, 128);
+  const long nct = (n + 127) / 128;
+  p.splits = (int)std::max<long>(1, std::min<long>(nct, tt_ceil_div(1024, std::max(p.rb, 1))));
+  p.per = tt_ceil_div(nct, p.splits);
+  p.splits = tt_ceil_div(nct, std::max(p.per, 1));
+  return p;
+}
+}  // namespace
+
+// ws: row partials pm, pl [splits][n], diag [n], column partials cpm, cpl [rb][n]
+extern "C" long tt_infonce_sym_fwd_ws_size(long n, int h) {
+  (void)h;
+  if (n <= 0) return 256;
+  const SymFwdPlan p = sym_fwd_plan(n);
+  return (2L * p.splits * n + n + 2L * p.rb * n) * (long)sizeof(float);
+}
+
+extern "C" int tt_infonce_sym_fwd(int dtype, const void* qn, const void* dn, long n, int h, float inv_tau,
+                                  float* lse_row, float* lse_col, float* row_loss, void* ws, void* stream) {
+  TT_CHECK_ARG(dtype == TT_DT_F32 || dtype == TT_DT_BF16, "tt_infonce_sym_fwd: bad dtype");
+  TT_CHECK_ARG(h > 0 && (h * esize(dtype)) % 16 == 0, "tt_infonce_sym_fwd: h=%d misaligned", h);
+  TT_CHECK_ARG(n >= 0 && n <= 65535L * 128, "tt_infonce_sym_fwd: n=%ld out of range", n);
+  if (n == 0) return 0;
+  TT_CHECK_ARG(ws != nullptr, "tt_infonce_sym_fwd: null workspace");
+  hipStream_t st = (hipStream_t)stream;
+  const SymFwdPlan p = sym_fwd_plan(n);
+  float* pm = static_cast<float*>(ws);
+  float* pl = pm + (long)p.splits * n;
+  float* diag = pl + (long)p.splits * n;
+  float* cpm = diag + n;
+  float* cpl = cpm + (long)p.rb * n;
+  dim3 grid(p.splits, p.rb);
   if (dtype == TT_DT_BF16)
-    hipLaunchKernelGGL(infonce_dscore_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)qn, bq,
-                       (const bf16_t*)dn, nd, h, inv_tau, offdiag_sub, label_offset, lse, gscale, ldds, (bf16_t*)ds);
+    hipLaunchKernelGGL(infonce_sym_fwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)qn, (const bf16_t*)dn,
+                       n, h, inv_tau, p.per, pm, pl, cpm, cpl, diag);
   else
-    hipLaunchKernelGGL(infonce_dscore_kernel<float>, grid, dim3(256), 0, st, (const float*)qn, bq, (const float*)dn,
-                       nd, h, inv_tau, offdiag_sub, label_offset, lse, gscale, ldds, (float*)ds);
-  TT_CHECK_LAUNCH("infonce_dscore_kernel");
-  // dqn = inv_tau * dS dn   (NN)
-  {
-    tt_gemm_batch g{};
-    g.a[0] = ds; g.b[0] = dn; g.c[0] = dqn;
-    const int sp = tt_gemm_pick_splits((int)bq, h, (int)nd, 1);
-    TT_PROPAGATE(tt_gemm(dtype, TT_DT_F32, 0, 1, (int)bq, h, (int)nd, &g, 1, ldds, h, h, inv_tau, 0, 0, 0, 0, 0.f, sp,
-                         sk, stream));
-  }
-  // ddn = inv_tau * dS^T qn (TN)
-  {
-    tt_gemm_batch g{};
-    g.a[0] = ds; g.b[0] = qn; g.c[0] = ddn;
-    const int sp = tt_gemm_pick_splits((int)nd, h, (int)bq, 1);
-    TT_PROPAGATE(tt_gemm(dtype, TT_DT_F32, 1, 1, (int)nd, h, (int)bq, &g, 1, ldds, h, h, inv_tau, 0, 0, 0, 0, 0.f, sp,
-                         sk, stream));
-  }
+    hipLaunchKernelGGL(infonce_sym_fwd_kernel<float>, grid, dim3(256), 0, st, (const float*)qn, (const float*)dn, n,
+                       h, inv_tau, p.per, pm, pl, cpm, cpl, diag);
+  TT_CHECK_LAUNCH("infonce_sym_fwd_kernel");
+  hipLaunchKernelGGL(infonce_sym_finalize_kernel, dim3(tt_ceil_div(n, 256)), dim3(256), 0, st, pm, pl, p.splits, cpm,
+                     cpl, p.rb, n, diag, lse_row, lse_col, row_loss);
+  TT_CHECK_LAUNCH("infonce_sym_finalize_kernel");
   return 0;
+}
+
+extern "C" long tt_infonce_sym_bwd_ws_size(int dtype, long n, int h) {
+  if (n <= 0) return 256;
+  return tt_infonce_bwd_ws_size(dtype, n, n, h);
+}
+
+extern "C" int tt_infonce_sym_bwd(int dtype, const void* qn, const void* dn, long n, int h, float inv_tau,
+                                  const float* lse_row, const float* lse_col, const float* gscale, float* dqn,
+                                  float* ddn, void* ws, void* stream) {
+  TT_CHECK_ARG(dtype == TT_DT_F32 || dtype == TT_DT_BF16, "tt_infonce_sym_bwd: bad dtype");
+  TT_CHECK_ARG(h > 0 && (h * esize(dtype)) % 16 == 0, "tt_infonce_sym_bwd: h=%d misaligned", h);
+  TT_CHECK_ARG(n >= 0 && n <= 65535L * 128, "tt_infonce_sym_bwd: n=%ld out of range", n);
+  if (n == 0) return 0;
+  TT_CHECK_ARG(ws != nullptr, "tt_infonce_sym_bwd: null workspace");
+  hipStream_t st = (hipStream_t)stream;
+  if (use_flash(dtype, h)) {
+    TT_CHECK_ARG((((uintptr_t)qn | (uintptr_t)dn) & 15) == 0, "tt_infonce_sym_bwd: bf16 rows must be 16-byte aligned");
+    const bf16_t* q = static_cast<const bf16_t*>(qn);
+    const bf16_t* d = static_cast<const bf16_t*>(dn);
+    float* slab = static_cast<float*>(ws);
+    if (h == 256) {
+      TT_PROPAGATE((flash_role<256, true, true>(q, n, d, n, inv_tau, 0.f, 0, lse_row, gscale, dqn, slab, st, lse_col)));
+      TT_PROPAGATE((flash_role<256, false, true>(q, n, d, n, inv_tau, 0.f, 0, lse_row, gscale, ddn, slab, st, lse_col)));
+    } else {
+      TT_PROPAGATE((flash_role<128, true, true>(q, n, d, n, inv_tau, 0.f, 0, lse_row, gscale, dqn, slab, st, lse_col)));
+      TT_PROPAGATE((flash_role<128, false, true>(q, n, d, n, inv_tau, 0.f, 0, lse_row, gscale, ddn, slab, st, lse_col)));
+    }
+    return 0;
+  }
+  return infonce_bwd_materialised<true>(dtype, qn, n, dn, n, h, inv_tau, 0.f, 0, lse_row, lse_col, gscale, dqn, ddn, ws,
+                                        stream);
 }
 
 // ws: the score block S [bq, nd] fp32, then the per-chunk candidates (values, indices)

@@ -106,6 +106,89 @@ class InfoNCELoss(nn.Module):
         return _finish_loss(s, 1.0 / (query_vec.shape[0] * world), self.process_group)
 
 
+class _SymCE(torch.autograd.Function):
+    """sum_i ((lse_row_i - S_ii) + (lse_col_i - S_ii)) / 2 over the square S = inv_tau qn dn^T
+    (one process): tt_infonce_sym_fwd / _bwd, both LSE vectors saved for the backward."""
+
+    @staticmethod
+    def forward(ctx, q, d, inv_tau, eps, do_norm, dt):
+        _lib.require_gpu(q, d)
+        q = q.float().contiguous()
+        d = d.float().contiguous()
+        if q.dim() != 2 or q.shape != d.shape:
+            raise _lib.TTError(f"SymmetricInfoNCELoss expects two [B, h] batches of one shape, got "
+                               f"{tuple(q.shape)} and {tuple(d.shape)}")
+        B, h = q.shape
+        if do_norm:
+            qn, qn32, qnorm = ops.l2norm_fwd(q, eps, dt)
+            dn, dn32, dnorm = ops.l2norm_fwd(d, eps, dt)
+        else:
+            qn, qn32, qnorm = (q if dt == torch.float32 else q.to(dt)), q, None
+            dn, dn32, dnorm = (d if dt == torch.float32 else d.to(dt)), d, None
+        lse_row = torch.empty(B, dtype=torch.float32, device=q.device)
+        lse_col = torch.empty(B, dtype=torch.float32, device=q.device)
+        row = torch.empty(B, dtype=torch.float32, device=q.device)
+        lib = _lib.load()
+        ws = torch.empty(lib.tt_infonce_sym_fwd_ws_size(B, h), dtype=torch.uint8, device=q.device)
+        esz = 2 if dt == torch.bfloat16 else 4
+        with timing.region("infonce_sym_fwd", 1, 2.0 * B * B * h, float(esz * 2 * B * h + 12 * B)):
+            call("tt_infonce_sym_fwd", dtype_code(dt), qn.data_ptr(), dn.data_ptr(), B, h, inv_tau,
+                 lse_row.data_ptr(), lse_col.data_ptr(), row.data_ptr(), ws.data_ptr(), stream_ptr(q.device))
+        out = torch.empty((), dtype=torch.float32, device=q.device)
+        ops.total(row, 1.0, out)
+        ctx.save = (qn, qn32, qnorm, dn, dn32, dnorm, lse_row, lse_col)
+        ctx.cfg = (inv_tau, eps, do_norm, dt)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        qn, qn32, qnorm, dn, dn32, dnorm, lse_row, lse_col = ctx.save
+        inv_tau, eps, do_norm, dt = ctx.cfg
+        B, h = qn.shape
+        gdev = gout.detach().float().reshape(1).contiguous()  # read by the kernels: no host sync
+        dqn = torch.empty(B, h, dtype=torch.float32, device=qn.device)
+        ddn = torch.empty(B, h, dtype=torch.float32, device=qn.device)
+        lib = _lib.load()
+        ws = torch.empty(lib.tt_infonce_sym_bwd_ws_size(dtype_code(dt), B, h), dtype=torch.uint8, device=qn.device)
+        call("tt_infonce_sym_bwd", dtype_code(dt), qn.data_ptr(), dn.data_ptr(), B, h, inv_tau, lse_row.data_ptr(),
+             lse_col.data_ptr(), gdev.data_ptr(), dqn.data_ptr(), ddn.data_ptr(), ws.data_ptr(),
+             stream_ptr(qn.device))
+        if do_norm:
+            dq = ops.l2norm_bwd(dqn, qn32, qnorm, eps)
+            dd = ops.l2norm_bwd(ddn, dn32, dnorm, eps)
+        else:
+            dq, dd = dqn, ddn
+        return dq, dd, None, None, None, None
+
+
+class SymmetricInfoNCELoss(nn.Module):
+    """simple_two_tower.py:68-78: (CE(S, arange) + CE(S^T, arange)) / 2 with S = q·dᵀ /
+    temperature (the CLIP-style symmetric contrastive loss). The reference's inputs are
+    already normalised, so normalize defaults to False; True normalises first (tt_l2norm).
+    One process: both directions from one score pass (tt_infonce_sym_fwd/_bwd). With a
+    process group of world > 1: the exact composition of the one-directional kernels,
+    (CE(q, gather(d)) + CE(d, gather(q))) / 2 over the global batch."""
+
+    def __init__(self, temperature=0.1, normalize=False, compute_dtype=None, process_group=None):
+        super().__init__()
+        self.temperature = temperature
+        self.normalize = normalize
+        self.compute_dtype = compute_dtype
+        self.process_group = process_group
+
+    def forward(self, query_vec, doc_vec):
+        dt = _dt_of(query_vec, self.compute_dtype)
+        inv_tau = 1.0 / self.temperature
+        B = query_vec.shape[0]
+        if not dist.active(self.process_group):
+            return _SymCE.apply(query_vec, doc_vec, inv_tau, 1e-12, bool(self.normalize), dt) / B
+        _, world = dist.rank_world(self.process_group)
+        g = self.process_group
+        s = 0.5 * (_NormCE.apply(query_vec, doc_vec, inv_tau, 0.0, 1e-12, bool(self.normalize), dt, g)
+                   + _NormCE.apply(doc_vec, query_vec, inv_tau, 0.0, 1e-12, bool(self.normalize), dt, g))
+        return _finish_loss(s, 1.0 / (B * world), g)
+
+
 class _MarginFn(torch.autograd.Function):
     """sum_i relu(margin - cos(q_i, dpool[lab_i]) + mean_j cos(q_i, dpool[idx_ij]))."""
 

@@ -3,6 +3,10 @@
 Same hyper-parameters and update formula as torch.optim.Adam (non-amsgrad,
 non-maximize); state lives in fp32 tensors per parameter ('exp_avg', 'exp_avg_sq',
 'step' like torch, so optimizer.state_dict() keeps torch's structure).
+
+AdamW (simple_two_tower.py:193) is the same step with decoupled weight decay
+(tt_adamw_multi); clip_grad_norm_ (simple_two_tower.py:239) is torch's rule in three
+launches for up to 48 gradients, the norm staying on the device.
 """
 from __future__ import annotations
 
@@ -17,6 +21,8 @@ _MAXT = 48
 
 
 class Adam(torch.optim.Optimizer):
+    _KERNEL = "tt_adam_multi"
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         if lr < 0.0 or eps < 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
             raise ValueError("invalid Adam hyper-parameter")
@@ -71,7 +77,7 @@ class Adam(torch.optim.Optimizer):
                     n = len(chunk)
                     arr = lambda xs: (ctypes.c_void_p * n)(*[x.data_ptr() for x in xs])
                     sizes = (ctypes.c_long * n)(*[p.numel() for p in chunk])
-                    call("tt_adam_multi", arr(chunk), arr([p.grad for p in chunk]),
+                    call(self._KERNEL, arr(chunk), arr([p.grad for p in chunk]),
                          arr([self.state[p]["exp_avg"] for p in chunk]),
                          arr([self.state[p]["exp_avg_sq"] for p in chunk]), sizes, n, group["lr"], b1, b2,
                          group["eps"], group["weight_decay"], step, guard.data_ptr(), stream_ptr(dev))
@@ -89,3 +95,47 @@ class Adam(torch.optim.Optimizer):
                 g.zero_()  # stream-ordered after every launch above
             self._guard_reads.append((ev, word, plist))
         return loss
+
+
+class AdamW(Adam):
+    """torch.optim.AdamW's defaults and update (decoupled weight decay: p *= 1 - lr * wd
+    before the Adam update, the gradient untouched); everything else is Adam's step."""
+    _KERNEL = "tt_adamw_multi"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm: float) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_(parameters, max_norm) (2-norm, error_if_nonfinite
+    False) on the device: the squared norm of every gradient (tt_grad_norm_multi), then
+    g *= min(1, max_norm / (norm + 1e-6)) (tt_clip_scale_multi). Returns the total norm as
+    a device tensor; nothing waits on the host. Gradients must be contiguous fp32."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        return torch.zeros(())
+    _lib.require_gpu(*grads)
+    dev = grads[0].device
+    for g in grads:
+        if g.dtype != torch.float32 or not g.is_contiguous() or g.device != dev:
+            raise _lib.TTError("two_towers_amd clip_grad_norm_ expects contiguous fp32 gradients on one device")
+    lib = _lib.load()
+    st = stream_ptr(dev)
+    sumsq = torch.empty(1, dtype=torch.float32, device=dev)
+    total = torch.empty((), dtype=torch.float32, device=dev)
+    chunks = [grads[i:i + _MAXT] for i in range(0, len(grads), _MAXT)]
+    args = []
+    for chunk in chunks:
+        n = len(chunk)
+        args.append(((ctypes.c_void_p * n)(*[g.data_ptr() for g in chunk]),
+                     (ctypes.c_long * n)(*[g.numel() for g in chunk]), n))
+    for i, (ptrs, sizes, n) in enumerate(args):
+        ws = torch.empty(lib.tt_grad_norm_ws_size(sizes, n), dtype=torch.uint8, device=dev)
+        call("tt_grad_norm_multi", ptrs, sizes, n, int(i > 0), sumsq.data_ptr(), ws.data_ptr(), st)
+    for ptrs, sizes, n in args:
+        call("tt_clip_scale_multi", ptrs, sizes, n, sumsq.data_ptr(), float(max_norm), total.data_ptr(), st)
+    torch.autograd.graph.increment_version(grads)
+    return total

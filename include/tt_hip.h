@@ -441,6 +441,44 @@ int tt_topk_rows(const float* S, long rows, long cols, long ld, long label_offse
                  int32_t* idx, float* val, void* ws, void* stream);
 long tt_topk_rows_ws_size(long rows, long cols, int k);
 
+/* Full ranks (validate_margin.py:11-54, compute_mrr): the 1-based position of a query's
+ * first relevant document among ALL N documents, no top-k cutoff, in two steps so that a
+ * corpus can be passed in blocks or shards. qn [Q, h], dn [N, h] dtype rows (cosine for
+ * normalised rows), both 16-byte aligned, h % 8 == 0 (else TT_EINVAL).
+ *
+ * Column j "beats" (theta, t) when s_j > theta, or s_j == theta and j < t: the project's
+ * order, value descending and equal scores towards the lower column. -0.0 == +0.0; NaN
+ * inputs are unspecified. rank = 1 + #{j beating the best relevant document}.
+ *
+ * tt_rank_best_relevant: per query the best relevant document, theta[i] = its score and
+ * tcol[i] = its column (the largest score over the row's relevant columns, ties to the
+ * lowest column); tcol = -1 and theta = 0 for a row without one. Relevance is CSR on the
+ * device: rel_ptr [Q + 1] int32 (ascending, rel_ptr[0] the row's first entry), rel_idx
+ * int32 columns in [0, N), in any order. The arrays live in device memory, so the host
+ * cannot check them: an entry outside [0, N) is skipped, as if it were absent. Every theta
+ * is formed with the MFMA instruction, operand orientation and k order of the scan and of
+ * tt_gemm, so it has the very bits that tt_rank_count compares against -- document tcol
+ * itself and exact duplicates of it land on the right side. ws is unused (may be NULL).
+ *
+ * tt_rank_count: for each query with tcol >= 0, count[i] = (accumulate ? count[i] : 0) +
+ * #{j in [0, N) : column col_offset + j beats (theta[i], tcol[i])}; tcol is a global column,
+ * dn holds global columns col_offset .. col_offset + N. A query with tcol < 0 gets 0
+ * (accumulate: is left alone). Counting consecutive blocks with accumulate gives exactly
+ * the count of one call over the whole matrix: the counts are integers (int32 atomic adds
+ * of the column splits' partial counts), so no order of summation changes them, and
+ * nothing depends on the previous contents of ws. Q = 0 and N = 0 are no-ops.
+ * bf16 with h in {128, 256, 512}: the streamed MFMA scan of tt_hardneg_topk with a counting
+ * epilogue, no score is stored. Other shapes, or option rank_gemm = 1: tt_gemm into a row
+ * block of ws (at most 1 GiB, rows chunked) and a count over the stored rows; the same
+ * counts, bit for bit. ws: tt_rank_count_ws_size bytes. */
+int tt_rank_best_relevant(int dtype, const void* qn, long Q, const void* dn, long N, int h,
+                          const int32_t* rel_ptr, const int32_t* rel_idx, float* theta, int32_t* tcol,
+                          void* ws, void* stream);
+int tt_rank_count(int dtype, const void* qn, long Q, const void* dn, long N, int h, long col_offset,
+                  const float* theta, const int32_t* tcol, int32_t* count, int accumulate, void* ws,
+                  void* stream);
+long tt_rank_count_ws_size(int dtype, long Q, long N, int h);
+
 /* MarginRankingLoss with explicit negatives (enhanced_two_tower.py:102-121) on
  * normalised vectors: pos_i = qn_i.dn_{label_offset+i}, negm_i = mean_j qn_i.dn_{idx[i,j]},
  * row_loss_i = max(margin - pos_i + negm_i, 0). Negatives are rows of dn. */

@@ -13,6 +13,8 @@ from .losses import (HardNegativeMarginLoss, InfoNCELoss, MarginRankingLoss, Sym
                      get_hard_negatives, mine_hard_negatives)
 from .model import EnhancedTwoTower, EnhancedTwoTowerModel
 from .optim import Adam, AdamW, clip_grad_norm_
+from .retrieval import (first_relevant_rank, mrr_from_ranks, recall_from_ranks, relevance_csr,
+                        validate_full_rank)
 from .simple import SimpleTwoTower
 from ._lib import GruTimeoutError
 from .towers import check_gru_status
@@ -22,6 +24,7 @@ __all__ = [
     "get_hard_negatives", "mine_hard_negatives", "EnhancedDataset", "EnhancedIdDataset", "MSMarcoDataset",
     "Vocab", "encode_ids", "encode_batch", "load_word2vec", "load_ms_marco_train", "pairs_from_msmarco", "Adam",
     "TwoTowerModel", "SimpleDataset", "MarginIdDataset", "margin_ids", "check_gru_status", "GruTimeoutError",
-    "SimpleTwoTower", "SymmetricInfoNCELoss", "AdamW", "clip_grad_norm_",
+    "SimpleTwoTower", "SymmetricInfoNCELoss", "AdamW", "clip_grad_norm_", "relevance_csr", "first_relevant_rank",
+    "mrr_from_ranks", "recall_from_ranks", "validate_full_rank",
 ]
 __version__ = "0.1.0"

@@ -181,6 +181,11 @@ _SIGS = {
     "tt_topk_rows": (c_int, [c_void_p, c_long, c_long, c_long, c_long, c_int, c_void_p, c_void_p, c_void_p,
                              c_void_p]),
     "tt_topk_rows_ws_size": (c_long, [c_long, c_long, c_int]),
+    "tt_rank_best_relevant": (c_int, [c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p]),
+    "tt_rank_count": (c_int, [c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_long, c_void_p, c_void_p, c_void_p,
+                              c_int, c_void_p, c_void_p]),
+    "tt_rank_count_ws_size": (c_long, [c_int, c_long, c_long, c_int]),
     "tt_margin_fwd": (c_int, [c_void_p, c_long, c_void_p, c_long, c_int, c_long, c_void_p, c_int, c_float,
                               c_void_p, c_void_p]),
     "tt_margin_bwd": (c_int, [c_void_p, c_long, c_void_p, c_long, c_int, c_long, c_void_p, c_int, c_float,

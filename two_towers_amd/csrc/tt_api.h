@@ -54,6 +54,7 @@ enum Opt {
                         // round as half tiles (2: whole tiles only, 3: half tiles only; 0: off)
   OPT_GRU_YPREV,        // 1: the training step stores the GRU layer outputs in the previous-state layout
                         // (tt_gru_fwd_yprev) where tt_gru_yprev_supported, so dW_hh is a plain TN GEMM; 0: Y as h_t
+  OPT_RANK_GEMM,        // 1: full-rank counts through tt_gemm + a pass over the stored rows, no scan
   OPT_N
 };
 int opt(Opt o);

@@ -45,7 +45,7 @@ constexpr OptDef kOpts[OPT_N] = {
     {"gemm_iepi", "TT_GEMM_IEPI", 1},             {"bres_rows", "TT_BRES_ROWS", 32},
     {"hn_scan_v", "TT_HN_SCAN_V", 5},             {"gemm_w4", "TT_GEMM_W4", 0},
     {"bres_form", "TT_BRES_FORM", 1},             {"wgrad_tall", "TT_WGRAD_TALL", 1},
-    {"gru_yprev", "TT_GRU_YPREV", 1},
+    {"gru_yprev", "TT_GRU_YPREV", 1},             {"rank_gemm", "TT_RANK_GEMM", 0},
 };
 struct OptTable {
   std::atomic<int> v[OPT_N];

@@ -20,6 +20,11 @@
 //                   ranked; k x 64 candidates per row.
 //   4. hn_final   : per row, top-k of its candidates (value desc, column asc).
 // Work: step 1 is the whole contraction (2 B N h FLOPs); steps 2-4 touch B k 64 h.
+//
+// Full ranks (validate_margin.py:11-54, no top-k cutoff): rank = 1 + the documents that beat
+// the query's best relevant one. rank_best_kernel forms that document's score with the
+// scan's MFMA sequence (as hn_rescore does); the count is step 1's tile loop with a counting
+// epilogue (hn_scan_kernel EPI 1), or tt_gemm + rank_count_rows_kernel for the other shapes.
 #include <float.h>
 #include <stdlib.h>
 
@@ -37,6 +42,12 @@ namespace {
 #endif
 #ifndef HN_Q64_PF  // fragment prefetch distance (k-steps) of the 64-query scan: 0 keeps it spill-free
 #define HN_Q64_PF 0
+#endif
+#ifndef RANK_FAST  // counting epilogue: 1 = one compare per element wherever no lane's threshold column is
+#define RANK_FAST 1  // near (41.1 us at 8192^2 x 256, 267 us at 8192 x 65536); 0 = the general form everywhere (44.5, 289)
+#endif
+#ifndef RANK_PF  // fragment prefetch distance (k-steps) of the h 256 counting scan: 2 measured slower with either
+#define RANK_PF 1  // epilogue (48.2 us with 8 registers spilled into the tile loop; 41.5 us spill-free with RANK_FAST)
 #endif
 constexpr int SC_COLS = 64;     // document columns per tile (= per chunk)
 constexpr int SC_TPS_MAX = 32;  // tiles per workgroup (chunk-max staging)
@@ -151,15 +162,28 @@ TT_DEV uint4 ld_frag(const bf16_t* __restrict__ base, long row, long nrows, int 
 // 64-document tile and the chunk maximum is 15 lane-local max + two permlane swaps.
 // Grid: row tiles x column splits, 1-D: block b -> split b % S (a split's workgroups
 // share one XCD label and its document slice stays in that L2), row tile b / S.
-template <int KS, int V = 0>
+// EPI 1 (full ranks, tt_rank_count): the same tile loop with a counting epilogue. Each lane
+// compares its 16 scores of a tile with its query's threshold (theta, tcol) and keeps one
+// integer count per query block over all of its tiles; nothing is staged or stored per
+// tile. label_off then carries the global index of column 0 (col_offset, nothing is masked)
+// and CM the int32 counts, which take one integer atomic add per (row, split) at the end.
+struct RankIn {
+  const float* theta;
+  const int32_t* tcol;
+};
+
+template <int KS, int V = 0, int EPI = 0>
 __global__ __launch_bounds__(ScanCfg<KS>::WAVES * 64, 1) void hn_scan_kernel(const bf16_t* __restrict__ Q, long bq,
                                                                  const bf16_t* __restrict__ D, long nd,
                                                                  long label_off, int S, int tps, long nch,
-                                                                 float* __restrict__ CM, int map) {
+                                                                 float* __restrict__ CM, int map, RankIn rk) {
   using TI = ScanTile<KS>;
   using Cfg = ScanCfg<KS, V>;
+  static_assert(EPI == 0 || (V == 0 && !Cfg::SINGLE && !Cfg::DIRECT), "the counting epilogue rides the pair-retiring body");
   constexpr int SC_WAVES = Cfg::WAVES, SC_ROWS = Cfg::ROWS, SC_SLOTS = Cfg::SLOTS;
-  constexpr int SC_RB = Cfg::RB, NDB = Cfg::NDB, DH = Cfg::DH, QW = Cfg::QW, TPSM = Cfg::TPSM;
+  constexpr int SC_RB = Cfg::RB, NDB = Cfg::NDB, DH = Cfg::DH, QW = Cfg::QW, TPSM = EPI ? 0 : Cfg::TPSM;
+  const long col_off = EPI ? label_off : 0;
+  if constexpr (EPI) label_off = -1;
   // tile ring + chunk maxima [tile][row]: 4 x 32 KiB + 32 KiB (h 256) or 2 x 64 KiB + 16
   // KiB (h 512), one workgroup per CU
   __shared__ __attribute__((aligned(16))) char lds[SC_SLOTS * TI::BYTES + TPSM * SC_ROWS * 4];
@@ -216,6 +240,27 @@ __global__ __launch_bounds__(ScanCfg<KS>::WAVES * 64, 1) void hn_scan_kernel(con
     for (int ks = 0; ks < KS; ++ks)
       asm volatile("" ::"v"(qa[qb][ks].x), "v"(qa[qb][ks].y), "v"(qa[qb][ks].z), "v"(qa[qb][ks].w));
   if constexpr (Cfg::DIRECT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tiles 0-3 landed
+  // counting epilogue: this lane's query of block qb is row0 + 16 qb + (lane & 15). th = its
+  // threshold score, trel = its threshold column relative to the lane's first document of
+  // the split's tile 0 (element e = 16 db + r of tile t is then column trel-relative
+  // 64 t + e), cnt = the documents that beat it so far. Rows past bq and rows without a
+  // relevant document (tcol < 0) count against +inf: nothing.
+  float th[SC_RB];
+  int trel[SC_RB];  // >= -1: every column at or below the lane's first one reads as "none below"
+  int cnt[SC_RB];
+  if constexpr (EPI) {
+#pragma unroll
+    for (int qb = 0; qb < SC_RB; ++qb) {
+      const long row = row0 + qb * 16 + (lane & 15);
+      const int tc = row < bq ? rk.tcol[row] : -1;
+      th[qb] = tc >= 0 ? rk.theta[row] : __builtin_inff();
+      const long tr = (long)tc - col_off - t0 * SC_COLS - (db0 * 16 + 4 * (lane >> 4));
+      trel[qb] = tr < -1 ? -1 : (int)tr;  // tc < 2^31; 64 t < 2^31 below, so the difference fits
+      cnt[qb] = 0;
+    }
+#pragma unroll
+    for (int qb = 0; qb < SC_RB; ++qb) asm volatile("" ::"v"(th[qb]), "v"(trel[qb]));  // retired here, as the query rows
+  }
   // CM rows of this workgroup through a buffer range: rows past bq store nothing (an
   // offset past num_records), so every wave issues the same number of store instructions
   const __amdgpu_buffer_rsrc_t rcm = tt_rsrc(CM);
@@ -283,7 +328,53 @@ __global__ __launch_bounds__(ScanCfg<KS>::WAVES * 64, 1) void hn_scan_kernel(con
       }
     }
   };
+  // Counting epilogue, documents [2 part, 2 part + 2) x 16 of tile t for query block qb:
+  // element e beats (theta, tcol) if it scores more, or the same at a lower column (e < tl).
+  // masked (the last, partial tile): elements at or past nd (e >= lim) are no documents.
+  auto count_part = [&](const f32x4 (&a)[NDB][SC_RB], int t, int qb, int part, bool masked) {
+    const int tl = trel[qb] - t * SC_COLS;  // e < tl: below 0 none, above 63 all
+    const long l = nd - (t0 + t) * SC_COLS - (db0 * 16 + 4 * (lane >> 4));
+    const int lim = !masked || l > SC_COLS ? SC_COLS : l < 0 ? 0 : (int)l;  // masked: wave-uniform
+    int c = 0;
+#if RANK_FAST
+    // The part's elements are e in [32 part, 32 part + 19]. A lane whose threshold column
+    // lies outside that span needs one compare per element: s > theta above the column,
+    // s >= theta below it, the latter as s > pred(theta), the next float below theta (exact
+    // for a normal theta; a theta within 2^-100 of zero takes the general form). The general
+    // form runs only where some lane of the wave has its column inside the span: for about
+    // 16 of the 2 nch parts of a query block.
+    const int e0 = 32 * part, e1 = 32 * part + 19;
+    const bool general = (tl > e0 && tl <= e1) || !(fabsf(th[qb]) >= 0x1p-100f);
+    if (!masked && __builtin_amdgcn_ballot_w64(general) == 0) {
+      const int bits = (int)__float_as_uint(th[qb]);
+      const float thr = tl > e1 ? __uint_as_float((uint32_t)(bits + (bits < 0 ? 1 : -1))) : th[qb];
+#pragma unroll
+      for (int db = 2 * part; db < 2 * part + 2; ++db)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) c += a[db][qb][r] > thr ? 1 : 0;
+      cnt[qb] += c;
+      return;
+    }
+#endif
+#pragma unroll
+    for (int db = 2 * part; db < 2 * part + 2; ++db)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float s = a[db][qb][r];
+        const int e = db * 16 + r;
+        const bool beats = s > th[qb] || (s == th[qb] && e < tl);
+        c += (beats && e < lim) ? 1 : 0;
+      }
+    cnt[qb] += c;
+  };
   auto chunk_max = [&](const f32x4 (&a)[NDB][SC_RB], int t, bool masked) {
+    if constexpr (EPI) {
+#pragma unroll
+      for (int qb = 0; qb < SC_RB; ++qb)
+#pragma unroll
+        for (int part = 0; part < NDB / 2; ++part) count_part(a, t, qb, part, masked);
+      return;
+    }
     const int n0 = (int)((t0 + t) * SC_COLS);
     const bool diag = label_off >= 0 && label_off + row0 < n0 + SC_COLS && n0 < label_off + row0 + SC_RB * 16;
 #pragma unroll
@@ -327,7 +418,9 @@ __global__ __launch_bounds__(ScanCfg<KS>::WAVES * 64, 1) void hn_scan_kernel(con
 #pragma unroll
       for (int qb = 0; qb < SC_RB; ++qb) acc[db][qb] = f32x4{0.f, 0.f, 0.f, 0.f};
     // fragment ring: k-steps PF ahead
-    constexpr int PF = Cfg::PF;
+    // (the h 256 count holds thresholds and counts on top of the 223 registers of the
+    // chunk-max form: two k-steps ahead it spills 8 of them into the tile loop, one does not)
+    constexpr int PF = EPI && KS == 8 ? RANK_PF : Cfg::PF;
     uint4 fa[PF + 1][NDB];
 #pragma unroll
     for (int ks = 0; ks < PF; ++ks)
@@ -342,6 +435,10 @@ __global__ __launch_bounds__(ScanCfg<KS>::WAVES * 64, 1) void hn_scan_kernel(con
     auto slice = [&](int i) {
       const int qb = i / NSQ, part = i % NSQ;
       if (qb >= SC_RB) return;
+      if constexpr (EPI) {
+        if (part < NSQ - 1) count_part(prev, t - 1, qb, part, false);
+        return;
+      }
       if (part < NSQ - 1) {
         const f32x4 x = prev[2 * part][qb], y = prev[2 * part + 1][qb];
         const float hm =
@@ -417,6 +514,19 @@ __global__ __launch_bounds__(ScanCfg<KS>::WAVES * 64, 1) void hn_scan_kernel(con
   }
   if constexpr (Cfg::DIRECT) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing zero-page / next-split DMAs land before exit
+    return;
+  }
+  if constexpr (EPI) {
+    // the four 16-lane groups hold the counts of the same 16 queries over different documents
+    int32_t* count = reinterpret_cast<int32_t*>(CM);
+#pragma unroll
+    for (int qb = 0; qb < SC_RB; ++qb) {
+      int c = cnt[qb];
+      c += __shfl_xor(c, 16, 64);
+      c += __shfl_xor(c, 32, 64);
+      const long row = row0 + qb * 16 + lane;
+      if (lane < 16 && row < bq && c != 0) atomicAdd(count + row, c);
+    }
     return;
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's ds_max (inline asm: not counted by hipcc)
@@ -611,7 +721,7 @@ void hn_scan_launch(const bf16_t* qn, long bq, const bf16_t* dn, long nd, long l
   int map = tt::opt(tt::OPT_HN_MAP);
   if (map == 2 && (p.RT % 2 != 0 || p.S % 4 != 0)) map = 0;
   hipLaunchKernelGGL((hn_scan_kernel<KS, V>), dim3((unsigned)(p.RT * p.S)), dim3(ScanCfg<KS, V>::WAVES * 64), 0, st, qn,
-                     bq, dn, nd, label_offset, (int)p.S, (int)p.tps, p.nch, CM, map);
+                     bq, dn, nd, label_offset, (int)p.S, (int)p.tps, p.nch, CM, map, RankIn{});
 }
 
 template <int KS>
@@ -662,6 +772,123 @@ int hn_run(const bf16_t* qn, long bq, const bf16_t* dn, long nd, long label_offs
   return 0;
 }
 
+// ---------------------------------------------------------------- full ranks
+// Better of two (score, column) pairs under the ranking order: score descending, equal
+// scores towards the lower column; a column < 0 is "none".
+TT_DEV void rank_better(float& s, int& c, float os, int oc) {
+  if (oc >= 0 && (c < 0 || os > s || (os == s && oc < c))) {
+    s = os;
+    c = oc;
+  }
+}
+
+// The best relevant document of each query: one wave per query, 16 of its relevant
+// documents per round as the A rows of the scan's transposed MFMA (C[doc][query]; the
+// query row is every B column), 16-byte chunk 4 ks + (lane >> 4) of a row per 64-byte
+// k-step -- the fragment k layout and k order of hn_scan_kernel / hn_rescore_kernel and of
+// the GEMM main loop (tt_gemm_core.h), so theta has the bits that tt_rank_count compares
+// against on either path. Chunks past h read as zeros, as the GEMM's K tail does.
+template <typename T>
+__global__ __launch_bounds__(256) void rank_best_kernel(const T* __restrict__ Q, long bq, const T* __restrict__ D,
+                                                        long nd, int h, const int32_t* __restrict__ rel_ptr,
+                                                        const int32_t* __restrict__ rel_idx,
+                                                        float* __restrict__ theta, int32_t* __restrict__ tcol) {
+  constexpr int EPC = Elt<T>::EPC;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= bq) return;
+  const int nks = (h + 4 * EPC - 1) / (4 * EPC);
+  const int p0 = rel_ptr[row], p1 = rel_ptr[row + 1];
+  float best = 0.f;
+  int bcol = -1;
+  for (int p = p0; p < p1; p += 16) {
+    const int pi = p + (lane & 15);
+    int doc = pi < p1 ? rel_idx[pi] : -1;
+    if (doc >= nd) doc = -1;
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int ks = 0; ks < nks; ++ks) {
+      const int e0 = (4 * ks + (lane >> 4)) * EPC;
+      uint4 qf = make_uint4(0, 0, 0, 0), df = make_uint4(0, 0, 0, 0);
+      if (e0 < h) {
+        qf = *reinterpret_cast<const uint4*>(Q + row * h + e0);
+        if (doc >= 0) df = *reinterpret_cast<const uint4*>(D + (long)doc * h + e0);
+      }
+      acc = ttg::mma<T>(df, qf, acc);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)  // C row 4 (lane >> 4) + r: the document that lane of the same index loaded
+      rank_better(best, bcol, acc[r], __shfl(doc, 4 * (lane >> 4) + r, 64));
+  }
+#pragma unroll
+  for (int o = 16; o < 64; o <<= 1) {
+    const float os = __shfl_xor(best, o, 64);
+    const int oc = __shfl_xor(bcol, o, 64);
+    rank_better(best, bcol, os, oc);
+  }
+  if (lane == 0) {
+    theta[row] = bcol >= 0 ? best : 0.f;
+    tcol[row] = bcol;
+  }
+}
+
+// Stored path: one wave per row of the score block S [rows, n] (leading dimension ld).
+__global__ __launch_bounds__(256) void rank_count_rows_kernel(const float* __restrict__ S, long rows, long n, long ld,
+                                                              long col_off, const float* __restrict__ theta,
+                                                              const int32_t* __restrict__ tcol,
+                                                              int32_t* __restrict__ count, int accumulate) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const int tc = tcol[row];
+  if (tc < 0) {
+    if (lane == 0 && !accumulate) count[row] = 0;
+    return;
+  }
+  const float th = theta[row];
+  const long tl = (long)tc - col_off;  // columns below it win ties
+  const float* sr = S + row * ld;
+  int c = 0;
+  for (long j0 = lane; j0 < n; j0 += 4 * 64) {
+    float v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = j0 + u * 64 < n ? sr[j0 + u * 64] : 0.f;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long j = j0 + u * 64;
+      c += (j < n && (v[u] > th || (v[u] == th && j < tl))) ? 1 : 0;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  if (lane == 0) count[row] = (accumulate ? count[row] : 0) + c;
+}
+
+template <int KS>
+int rank_scan_run(const bf16_t* qn, long bq, const bf16_t* dn, long nd, long col_offset, const float* theta,
+                  const int32_t* tcol, int32_t* count, hipStream_t st) {
+  // a count needs no per-tile staging, so a split may hold any number of tiles: as many
+  // splits as fill the 256 CUs, no more
+  const HnPlan p = hn_plan(bq, nd, 1, ScanCfg<KS>::ROWS, 1L << 30);
+  int map = tt::opt(tt::OPT_HN_MAP);
+  if (map == 2 && (p.RT % 2 != 0 || p.S % 4 != 0)) map = 0;
+  hipLaunchKernelGGL((hn_scan_kernel<KS, 0, 1>), dim3((unsigned)(p.RT * p.S)), dim3(ScanCfg<KS>::WAVES * 64), 0, st, qn,
+                     bq, dn, nd, col_offset, (int)p.S, (int)p.tps, p.nch, reinterpret_cast<float*>(count), map,
+                     RankIn{theta, tcol});
+  TT_CHECK_LAUNCH("hn_scan_kernel (count)");
+  return 0;
+}
+
+bool rank_fused(int dtype, int h) {
+  return tt::opt(tt::OPT_RANK_GEMM) != 1 && dtype == TT_BF16 && (h == 128 || h == 256 || h == 512);
+}
+
+constexpr long RANK_BLOCK_ELEMS = 1L << 28;  // the stored score block stays within 1 GiB
+long rank_rows_per(long Q, long N) {
+  long r = RANK_BLOCK_ELEMS / (N > 0 ? N : 1);
+  if (r < 1) r = 1;
+  return r < Q ? r : Q;
+}
+
 }  // namespace
 
 // Used by tt_hardneg_topk (tt_loss.hip) for bf16 operands with h in {128, 256, 512}.
@@ -684,4 +911,80 @@ int tt_hn_scan_topk(const void* qn, long bq, const void* dn, long nd, int h, lon
   if (h == 512) return hn_run<16>(q, bq, d, nd, label_offset, k, idx, val, w, st);
   if (h == 256) return hn_run<8>(q, bq, d, nd, label_offset, k, idx, val, w, st);
   return hn_run<4>(q, bq, d, nd, label_offset, k, idx, val, w, st);
+}
+
+// ---------------------------------------------------------------- full ranks: C ABI
+namespace {
+int rank_check(const char* what, int dtype, const void* qn, long Q, const void* dn, long N, int h) {
+  TT_CHECK_ARG(dtype == TT_DT_F32 || dtype == TT_DT_BF16, "%s: bad dtype %d", what, dtype);
+  TT_CHECK_ARG(Q >= 0 && N >= 0 && Q < (1L << 31) && N < (1L << 31), "%s: Q=%ld, N=%ld out of range", what, Q, N);
+  TT_CHECK_ARG(h > 0 && h % 8 == 0, "%s: h=%d must be a positive multiple of 8", what, h);
+  TT_CHECK_ARG((((uintptr_t)qn | (uintptr_t)dn) & 15) == 0, "%s: rows must be 16-byte aligned", what);
+  return 0;
+}
+}  // namespace
+
+extern "C" int tt_rank_best_relevant(int dtype, const void* qn, long Q, const void* dn, long N, int h,
+                                     const int32_t* rel_ptr, const int32_t* rel_idx, float* theta, int32_t* tcol,
+                                     void* ws, void* stream) {
+  (void)ws;
+  TT_PROPAGATE(rank_check("tt_rank_best_relevant", dtype, qn, Q, dn, N, h));
+  if (Q == 0) return 0;
+  TT_CHECK_ARG(rel_ptr && theta && tcol && qn && (dn || N == 0), "tt_rank_best_relevant: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)tt_ceil_div(Q, 4));
+  if (dtype == TT_DT_BF16)
+    hipLaunchKernelGGL(rank_best_kernel<bf16_t>, grid, dim3(256), 0, st, static_cast<const bf16_t*>(qn), Q,
+                       static_cast<const bf16_t*>(dn), N, h, rel_ptr, rel_idx, theta, tcol);
+  else
+    hipLaunchKernelGGL(rank_best_kernel<float>, grid, dim3(256), 0, st, static_cast<const float*>(qn), Q,
+                       static_cast<const float*>(dn), N, h, rel_ptr, rel_idx, theta, tcol);
+  TT_CHECK_LAUNCH("rank_best_kernel");
+  return 0;
+}
+
+extern "C" long tt_rank_count_ws_size(int dtype, long Q, long N, int h) {
+  if (Q <= 0 || N <= 0 || rank_fused(dtype, h)) return 256;
+  return al256(rank_rows_per(Q, N) * N * 4);
+}
+
+extern "C" int tt_rank_count(int dtype, const void* qn, long Q, const void* dn, long N, int h, long col_offset,
+                             const float* theta, const int32_t* tcol, int32_t* count, int accumulate, void* ws,
+                             void* stream) {
+  TT_PROPAGATE(rank_check("tt_rank_count", dtype, qn, Q, dn, N, h));
+  TT_CHECK_ARG(col_offset >= 0 && col_offset + N < (1L << 31), "tt_rank_count: col_offset=%ld + N=%ld out of range",
+               col_offset, N);
+  if (Q == 0) return 0;
+  TT_CHECK_ARG(theta && tcol && count && qn, "tt_rank_count: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  if (N == 0) {  // no column counted: only the overwrite is left
+    if (!accumulate) TT_CHECK_HIP(hipMemsetAsync(count, 0, Q * 4, st));
+    return 0;
+  }
+  TT_CHECK_ARG(dn != nullptr, "tt_rank_count: null documents");
+  if (rank_fused(dtype, h)) {
+    if (!accumulate) TT_CHECK_HIP(hipMemsetAsync(count, 0, Q * 4, st));
+    const bf16_t* q = static_cast<const bf16_t*>(qn);
+    const bf16_t* d = static_cast<const bf16_t*>(dn);
+    if (h == 512) return rank_scan_run<16>(q, Q, d, N, col_offset, theta, tcol, count, st);
+    if (h == 256) return rank_scan_run<8>(q, Q, d, N, col_offset, theta, tcol, count, st);
+    return rank_scan_run<4>(q, Q, d, N, col_offset, theta, tcol, count, st);
+  }
+  TT_CHECK_ARG(ws != nullptr, "tt_rank_count: null workspace (tt_rank_count_ws_size bytes)");
+  float* S = static_cast<float*>(ws);
+  const long rows_per = rank_rows_per(Q, N);
+  const long esz = dtype == TT_DT_BF16 ? 2 : 4;
+  for (long r0 = 0; r0 < Q; r0 += rows_per) {
+    const long rows = Q - r0 < rows_per ? Q - r0 : rows_per;
+    tt_gemm_batch g{};
+    g.a[0] = static_cast<const char*>(qn) + r0 * h * esz;
+    g.b[0] = dn;
+    g.c[0] = S;
+    TT_PROPAGATE(tt_gemm(dtype, TT_DT_F32, 0, 0, (int)rows, (int)N, h, &g, 1, h, h, N, 1.f, 0, 0, 0, 0, 0.f, 1, nullptr,
+                         stream));
+    hipLaunchKernelGGL(rank_count_rows_kernel, dim3((unsigned)tt_ceil_div(rows, 4)), dim3(256), 0, st, S, rows, N, N,
+                       col_offset, theta + r0, tcol + r0, count + r0, accumulate);
+    TT_CHECK_LAUNCH("rank_count_rows_kernel");
+  }
+  return 0;
 }

@@ -532,6 +532,45 @@ long tt_grad_norm_ws_size(const long* sizes, int ntensors);
 int tt_clip_scale_multi(float* const* grads, const long* sizes, int ntensors, const float* sumsq,
                         float max_norm, float* total_norm_out, void* stream);
 
+/* ------------------------------------------------------- trainable embedding table */
+/* Segment sum of gradient rows by token id: rows[u, :] = sum of dx[perm[p], 0:e] over
+ * seg_ptr[u] <= p < seg_ptr[u+1], p ascending. dx fp32 [n, ldx] (the layer-0 data gradient,
+ * one row per token position); perm int32 [m]: the row numbers of dx ordered by token id
+ * (stable, pads removed); seg_ptr int32 [nseg + 1], strictly increasing from 0 to m: one
+ * segment per distinct id; rows fp32 [nseg, e], every row written whole (overwritten).
+ * A perm entry outside [0, n) adds nothing.
+ *  - fp32 accumulation, no float atomics;
+ *  - every element is a sum in an order fixed by (perm, seg_ptr) alone: workgroup k adds the
+ *    positions [k C, (k+1) C) (C = tt_embed_grad_chunk()) of each segment in order, and a
+ *    segment that reaches into several chunks is the sum of its per-chunk partials in chunk
+ *    order (second launch). Two calls give the same bits;
+ *  - ws: tt_embed_grad_ws_size(m, e) bytes holding those partials; only slots written by
+ *    the call are read, so nothing depends on its previous contents;
+ *  - nseg = 0, m = 0 and n = 0 are no-ops;
+ *  - any e >= 1: 16-byte loads when e % 4 == 0, ldx % 4 == 0 and dx, rows, ws are 16-byte
+ *    aligned, else a scalar path with the same sums. n, m < 2^31. */
+int tt_embed_grad_rows(const float* dx, long n, long ldx, const int32_t* perm, long m,
+                       const int32_t* seg_ptr, long nseg, int e, float* rows, void* ws, void* stream);
+long tt_embed_grad_ws_size(long m, int e);
+/* Sorted positions per workgroup of tt_embed_grad_rows (the chunk size C above). */
+int tt_embed_grad_chunk(void);
+
+/* torch.optim.SparseAdam's step (torch/optim/_functional.py sparse_adam) on the rows
+ * ids[0..nrows) (distinct, int32) of weight / exp_avg / exp_avg_sq (fp32 [vocab, e]) with
+ * the summed gradient rows (fp32 [nrows, e]):
+ *   dm = (g - m)(1-b1); dv = (g^2 - v)(1-b2); m += dm; v += dv;
+ *   w -= lr sqrt(1-b2^step)/(1-b1^step) * (m / (sqrt(v) + eps))
+ * (eps joins sqrt(v) before the bias corrections, which use the global step: not dense
+ * Adam's formula). Rows not named by ids are neither read nor written (lazy moments); an id
+ * outside [0, vocab) is skipped. copy (optional): the [vocab, ep] copy of weight in
+ * copy_dtype that tt_embed_gather reads; columns [0, e) of the touched rows are rewritten
+ * from the new fp32 values (round-to-nearest-even for bf16), columns e.. are left alone.
+ * skip as tt_adam_multi: non-zero at launch time means nothing changes. */
+int tt_sparse_adam_rows(float* weight, float* exp_avg, float* exp_avg_sq, long vocab, int e,
+                        const int32_t* ids, const float* rows, long nrows, int copy_dtype, void* copy,
+                        int ep, float lr, float beta1, float beta2, float eps, int step,
+                        const int32_t* skip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

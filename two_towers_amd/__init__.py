@@ -8,11 +8,12 @@ of enhanced_two_tower.py (and the margin family of margin_two_tower.py in .margi
 """
 from .data import (EnhancedDataset, EnhancedIdDataset, MSMarcoDataset, Vocab, encode_batch, encode_ids,
                    load_ms_marco_train, load_word2vec, pairs_from_msmarco)
+from .embedding import EmbeddingTable
 from .margin import MarginIdDataset, SimpleDataset, TwoTowerModel, margin_ids
 from .losses import (HardNegativeMarginLoss, InfoNCELoss, MarginRankingLoss, SymmetricInfoNCELoss,
                      get_hard_negatives, mine_hard_negatives)
 from .model import EnhancedTwoTower, EnhancedTwoTowerModel
-from .optim import Adam, AdamW, clip_grad_norm_
+from .optim import Adam, AdamW, SparseAdam, clip_grad_norm_
 from .retrieval import (first_relevant_rank, mrr_from_ranks, recall_from_ranks, relevance_csr,
                         validate_full_rank)
 from .simple import SimpleTwoTower
@@ -25,6 +26,6 @@ __all__ = [
     "Vocab", "encode_ids", "encode_batch", "load_word2vec", "load_ms_marco_train", "pairs_from_msmarco", "Adam",
     "TwoTowerModel", "SimpleDataset", "MarginIdDataset", "margin_ids", "check_gru_status", "GruTimeoutError",
     "SimpleTwoTower", "SymmetricInfoNCELoss", "AdamW", "clip_grad_norm_", "relevance_csr", "first_relevant_rank",
-    "mrr_from_ranks", "recall_from_ranks", "validate_full_rank",
+    "mrr_from_ranks", "recall_from_ranks", "validate_full_rank", "EmbeddingTable", "SparseAdam",
 ]
 __version__ = "0.1.0"

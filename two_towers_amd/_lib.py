@@ -202,6 +202,12 @@ _SIGS = {
     "tt_grad_norm_ws_size": (c_long, [POINTER(c_long), c_int]),
     "tt_clip_scale_multi": (c_int, [POINTER(c_void_p), POINTER(c_long), c_int, c_void_p, c_float, c_void_p,
                                     c_void_p]),
+    "tt_embed_grad_rows": (c_int, [c_void_p, c_long, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_void_p,
+                                   c_void_p, c_void_p]),
+    "tt_embed_grad_ws_size": (c_long, [c_long, c_int]),
+    "tt_embed_grad_chunk": (c_int, []),
+    "tt_sparse_adam_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p, c_void_p, c_long, c_int,
+                                    c_void_p, c_int, c_float, c_float, c_float, c_float, c_int, c_void_p, c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -33,6 +33,7 @@ from torch.utils.data import Dataset
 
 from . import _lib, dist, ops, timing
 from ._lib import Head1BwdIO, Head1FwdIO, call, dtype_code, stream_ptr
+from .embedding import EmbeddingTable, check_table, trainable_table
 from .losses import InfoNCELoss
 from .model import _GRU_ORDER
 from .towers import HEAD_DT, LN_EPS, TowerCfg, run_towers
@@ -169,10 +170,10 @@ class TwoTowerModel(nn.Module):
 
     def set_embedding_table(self, table: torch.Tensor | None):
         """Attach a device Word2Vec table [V, E]; [B, T] int token-id inputs (margin_ids)
-        then gather rows on the GPU."""
-        if table is not None and (table.dim() != 2 or table.shape[1] != self.embedding_dim):
-            raise ValueError(f"table must be [V, {self.embedding_dim}]")
-        self._table_src = table
+        then gather rows on the GPU. A tensor is frozen; an EmbeddingTable (embedding.py)
+        with trainable=True receives a sparse gradient and is never a submodule."""
+        check_table(table, self.embedding_dim)
+        self.__dict__["_table_src"] = table  # not through nn.Module.__setattr__: never a submodule
         self._table = None
         return self
 
@@ -180,6 +181,8 @@ class TwoTowerModel(nn.Module):
         if self._table_src is None:
             return None
         dt = self.compute_dtype
+        if isinstance(self._table_src, EmbeddingTable):
+            return self._table_src.device_copy(device, dt)
         ep = ops.pad_cols(self.embedding_dim, dt)
         t = self._table
         if t is None or t.dtype != dt or t.device != device or t.shape[1] != ep:
@@ -203,7 +206,8 @@ class TwoTowerModel(nn.Module):
             params.extend(getattr(e, n) for n in _GRU_ORDER)
         table = self._device_table(xs[0].device) if xs[0].dtype in (torch.int32, torch.int64) else None
         return run_towers(cfg, table, xs, params, getattr(self, "process_group", None),
-                          getattr(self, "overlap_grad_allreduce", False) and torch.is_grad_enabled())
+                          getattr(self, "overlap_grad_allreduce", False) and torch.is_grad_enabled(),
+                          emb=trainable_table(self, table))
 
     def _project(self, vecs):
         """The shared projection over the row-stacked towers; returns one [B_i, H] per tower."""

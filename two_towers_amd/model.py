@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import dist, ops
+from .embedding import EmbeddingTable, check_table, trainable_table
 from .towers import TowerCfg, run_towers
 
 
@@ -60,17 +61,18 @@ class EnhancedTwoTowerModel(nn.Module):
         self.overlap_grad_allreduce = overlap_grad_allreduce
         return self
 
-    def set_embedding_table(self, table: torch.Tensor | None):
+    def set_embedding_table(self, table: "torch.Tensor | EmbeddingTable | None"):
         """Attach a device Word2Vec table [V, E] (any float dtype); token-id inputs then
         gather rows on the GPU. Stored padded in the compute dtype (built on first use;
-        the source tensor may be dropped after that)."""
+        the source tensor may be dropped after that). A plain tensor is frozen; an
+        EmbeddingTable (embedding.py) with trainable=True receives a sparse gradient. The
+        module is kept out of the submodules, so the state_dict keys stay the reference's."""
         if table is None:
             self._table = None
-            self._table_src = None
+            self.__dict__["_table_src"] = None
             return self
-        if table.dim() != 2 or table.shape[1] != self.embedding_dim:
-            raise ValueError(f"table must be [V, {self.embedding_dim}]")
-        self._table_src = table
+        check_table(table, self.embedding_dim)
+        self.__dict__["_table_src"] = table  # not through nn.Module.__setattr__: never a submodule
         self._table = None
         return self
 
@@ -79,6 +81,8 @@ class EnhancedTwoTowerModel(nn.Module):
         if src is None:
             return None
         dt = self.compute_dtype
+        if isinstance(src, EmbeddingTable):
+            return src.device_copy(device, dt)
         ep = ops.pad_cols(self.embedding_dim, dt)
         t = self._table
         if t is None or t.dtype != dt or t.device != device or t.shape[1] != ep:
@@ -113,7 +117,8 @@ class EnhancedTwoTowerModel(nn.Module):
             params.extend(self._tower_params(w))
         table = self._device_table(xs[0].device) if xs[0].dtype in (torch.int32, torch.int64) else None
         return run_towers(cfg, table, xs, params, self.process_group,
-                          self.overlap_grad_allreduce and torch.is_grad_enabled())
+                          self.overlap_grad_allreduce and torch.is_grad_enabled(),
+                          emb=trainable_table(self, table))
 
     def encode_query(self, query_emb):
         return self._run(["query"], [query_emb])[0]

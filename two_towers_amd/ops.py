@@ -85,6 +85,64 @@ def embed_gather(table: torch.Tensor, ids: torch.Tensor, out: torch.Tensor):
          ids.data_ptr(), ids.numel(), out.data_ptr(), stream_ptr(out.device))
 
 
+def embed_plan(ids: torch.Tensor):
+    """(perm, seg_ptr, unique) of token ids for tt_embed_grad_rows: perm int32 [m] lists the
+    flat positions of the ids >= 0 ordered by id (stable), seg_ptr int32 [U + 1] delimits one
+    segment of perm per distinct id, unique int64 [U] are those ids, ascending. Index
+    plumbing only (torch sort / unique_consecutive); it depends on the ids alone."""
+    flat = ids.reshape(-1).to(torch.int64)
+    vals, order = torch.sort(flat, stable=True)
+    keep = vals >= 0
+    vals, order = vals[keep], order[keep]
+    uniq, counts = torch.unique_consecutive(vals, return_counts=True)
+    seg_ptr = torch.zeros(uniq.numel() + 1, dtype=torch.int32, device=flat.device)
+    seg_ptr[1:] = torch.cumsum(counts, 0)
+    return order.to(torch.int32).contiguous(), seg_ptr, uniq
+
+
+def embed_grad_chunk() -> int:
+    """Sorted positions per workgroup of tt_embed_grad_rows."""
+    return int(_lib.load().tt_embed_grad_chunk())
+
+
+def embed_grad_rows(dx: torch.Tensor, perm: torch.Tensor, seg_ptr: torch.Tensor, e: int | None = None,
+                    rows: torch.Tensor | None = None, ws: torch.Tensor | None = None) -> torch.Tensor:
+    """rows[u] = sum of dx[perm[p], :e] over segment u of (perm, seg_ptr), fp32 [U, e]
+    (tt_embed_grad_rows: fixed summation order, no atomics)."""
+    assert dx.dtype == torch.float32 and dx.dim() == 2 and dx.stride(1) == 1
+    assert perm.dtype == torch.int32 and perm.is_contiguous() and seg_ptr.dtype == torch.int32 and seg_ptr.is_contiguous()
+    _lib.require_gpu(dx, perm, seg_ptr)
+    e = dx.shape[1] if e is None else e
+    u, m = seg_ptr.numel() - 1, perm.numel()
+    if rows is None:
+        rows = torch.empty(u, e, dtype=torch.float32, device=dx.device)
+    assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.numel() >= u * e
+    if ws is None:
+        ws = torch.empty(_lib.load().tt_embed_grad_ws_size(m, e), dtype=torch.uint8, device=dx.device)
+    assert ws.numel() * ws.element_size() >= _lib.load().tt_embed_grad_ws_size(m, e)
+    call("tt_embed_grad_rows", dx.data_ptr(), dx.shape[0], dx.stride(0), perm.data_ptr(), m, seg_ptr.data_ptr(), u, e,
+         rows.data_ptr(), ws.data_ptr(), stream_ptr(dx.device))
+    return rows
+
+
+def sparse_adam_rows(weight: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, ids: torch.Tensor,
+                     rows: torch.Tensor, copy: torch.Tensor | None, *, lr: float, beta1: float, beta2: float,
+                     eps: float, step: int, guard: torch.Tensor | None = None):
+    """torch.optim.SparseAdam's update of weight[ids] (and the moments) from the gradient rows;
+    copy: the padded compute-dtype table whose rows follow (tt_sparse_adam_rows)."""
+    v, e = weight.shape
+    for t in (weight, exp_avg, exp_avg_sq):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (v, e)
+    assert ids.dtype == torch.int32 and ids.is_contiguous()
+    assert rows.dtype == torch.float32 and rows.is_contiguous() and tuple(rows.shape) == (ids.numel(), e)
+    _lib.require_gpu(weight, exp_avg, exp_avg_sq, ids, rows, copy)
+    if copy is not None:
+        assert copy.is_contiguous() and copy.shape[0] == v and copy.shape[1] >= e
+    call("tt_sparse_adam_rows", weight.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), v, e, ids.data_ptr(),
+         rows.data_ptr(), ids.numel(), dtype_code(copy.dtype) if copy is not None else 0, ptr(copy),
+         copy.shape[1] if copy is not None else 0, lr, beta1, beta2, eps, step, ptr(guard), stream_ptr(weight.device))
+
+
 def pack_rows(src: torch.Tensor, out: torch.Tensor):
     assert src.dtype == torch.float32 and src.is_contiguous()
     e = src.shape[-1]

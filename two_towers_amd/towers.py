@@ -27,7 +27,7 @@ from dataclasses import dataclass
 import torch
 import torch.nn.functional as F
 
-from . import _lib, dist, ops, timing
+from . import _lib, dist, embedding, ops, timing
 from ._lib import GruBwdRec, GruFwdRec, GruInferRec, HeadBwdIO, HeadFwdIO, call, dtype_code, stream_ptr
 
 PARAMS_PER_TOWER = 22
@@ -601,13 +601,17 @@ def _weight_grads(cfg, B, T, dG, Xin, K, ldx, Y, kr=None, yprev=False):
 class TowersFn(torch.autograd.Function):
     """(x_0..x_{n-1}, params...) -> (vec_0..vec_{n-1}), vec_i = tower_i(x_i) as [B, h] fp32
     (cfg.head "proj2"), or the final bidirectional state cat(h_fwd, h_rev) as [B, 2H] fp32
-    (cfg.head "none": margin_two_tower.py:59-61, the head runs outside)."""
+    (cfg.head "none": margin_two_tower.py:59-61, the head runs outside).
+    An optional last argument is the fp32 master weight [V, E] of a trainable embedding
+    table (token-id inputs; `table` is its compute copy): it receives a coalesced sparse
+    gradient. Float inputs that require grad receive dL/dx as [B, T, E] fp32."""
 
     @staticmethod
     def forward(ctx, cfg: TowerCfg, table, group, cache_ok, *args):
         n = cfg.ntowers
-        xs, params = args[:n], args[n:]
-        _lib.require_gpu(*xs, *params)
+        emb_w = args[-1] if len(args) == n + n * cfg.nparams + 1 else None
+        xs, params = args[:n], args[n:n + n * cfg.nparams]
+        _lib.require_gpu(*xs, *params, emb_w)
         check_gru_status(wait=True)  # every earlier forward's column-split launches
         dt, E, H, h = cfg.dtype, cfg.E, cfg.H, cfg.h
         dev = xs[0].device
@@ -645,6 +649,21 @@ class TowersFn(torch.autograd.Function):
                 continue
             y = Y1[ti].view(B, T, 2 * H)
             hcat.append(torch.cat([y[:, T - 1, :H], y[:, 0, H:]], 1).to(HEAD_DT).contiguous())
+        # dL/dX0 is wanted by float inputs that require grad and by a trainable table; for the
+        # table, the index plumbing of its sparse gradient (which positions share a token id)
+        # depends on the ids alone and is built here, so that nothing but the segment-sum
+        # kernels sits between the data-gradient GEMM and the optimiser in the backward
+        ctx.x_grad = tuple(bool(ctx.needs_input_grad[4 + i]) and xs[i].is_floating_point() for i in range(n))
+        ctx.emb = None
+        if emb_w is not None and ctx.needs_input_grad[-1] and not xs[0].is_floating_point():
+            if tuple(emb_w.shape) != (table.shape[0], E) or emb_w.dtype != torch.float32:
+                raise _lib.TTError(f"embedding weight must be fp32 [{table.shape[0]}, {E}], got {emb_w.dtype} "
+                                   f"{tuple(emb_w.shape)}")
+            ids = torch.cat([x.reshape(-1) for x in xs])  # one row space: a token of both towers is one row
+            ctx.emb = (*ops.embed_plan(ids.masked_fill(ids >= table.shape[0], -1)), emb_w)
+            if not getattr(emb_w, "_tt_grad_hook", False):
+                emb_w.register_post_accumulate_grad_hook(embedding.keep_coalesced)
+                emb_w._tt_grad_hook = True
         ctx.cfg = cfg
         ctx.yprev = (yp0, yp1)
         ctx.group = group
@@ -764,6 +783,7 @@ class TowersFn(torch.autograd.Function):
         # ---- GRU layer 0
         dG0, dbih0, dbhh0 = _gru_layer_bwd(cfg, 0, B, T, S0, Y0, dY0, None, packs, yprev=yp0)
         del dY0
+        dxs, demb = _input_grads(ctx, cfg, B, T, Ep, dG0, packs)
         dWih0, dWhh0 = _weight_grads(cfg, B, T, dG0, X0, Ep, Ep, Y0, kr=E, yprev=yp0)
         gl0 = [{} for _ in range(n)]
         _layer_grads(gl0, 0, E, Ep, dWih0, dWhh0, dbih0, dbhh0)
@@ -782,7 +802,39 @@ class TowersFn(torch.autograd.Function):
         ctx.acts = None
         ctx.packs = None
         ctx.params = None
-        return (None, None, None, None, *([None] * n), *grads)
+        ctx.emb = None
+        tail = (demb,) if len(ctx.needs_input_grad) == 4 + n + len(grads) + 1 else ()
+        return (None, None, None, None, *dxs, *grads, *tail)
+
+
+def _input_grads(ctx, cfg, B, T, Ep, dG0, packs):
+    """The layer-0 data gradient dX0 = dG0[:, 0:6H] W_ih0 (fp32, the real E columns only), run
+    only when somebody wants it: as dL/dx [B, T, E] per float input that requires grad, and
+    summed by token id into the sparse gradient of a trainable table (one [ntowers B T, E]
+    buffer, so a token that occurs in both towers lands in one row). Returns (per-input
+    gradients or None, table gradient or None)."""
+    n, dt, E, H = cfg.ntowers, cfg.dtype, cfg.E, cfg.H
+    want_x, emb = any(ctx.x_grad), ctx.emb
+    if not want_x and emb is None:
+        return [None] * n, None
+    dev = dG0[0].device
+    BT = B * T
+    dX = _alloc((n * BT, E), torch.float32, dev)
+    parts = [dX[ti * BT:(ti + 1) * BT] for ti in range(n)]
+    esz = 2 if dt == torch.bfloat16 else 4
+    with timing.region("dgrad_l0", 1, 2.0 * BT * E * 6 * H * n, float(n * (esz * (BT * 6 * H + 6 * H * E) + 4 * BT * E))):
+        ops.gemm(dG0, [p.wih[0] for p in packs], parts, m=BT, n=E, k=6 * H, lda=8 * H, ldb=Ep, ldc=E,
+                 a_kouter=False, b_kouter=True, dtype=dt, out_dtype=torch.float32)
+    dxs = [parts[ti].view(B, T, E) if ctx.x_grad[ti] else None for ti in range(n)]
+    if emb is None:
+        return dxs, None
+    perm, seg_ptr, uniq, emb_w = emb
+    m, U, V = perm.numel(), uniq.numel(), emb_w.shape[0]
+    emb_w._tt_grad_ids = uniq  # embedding.keep_coalesced: autograd's stored copy drops the coalesced flag
+    with timing.region("embed_grad_rows", 2, 4.0 * (m + U) * E, float(4 * (m + U) * E + 4 * (m + U + 1)),
+                       kernel="embed_grad_chunk_kernel"):
+        rows = ops.embed_grad_rows(dX, perm, seg_ptr)
+    return dxs, torch.sparse_coo_tensor(uniq.unsqueeze(0), rows, (V, E), is_coalesced=True)
 
 
 def _layer_grads(gl, layer, E, Ep, dWih, dWhh, dbih, dbhh):
@@ -809,18 +861,29 @@ def _reduce_into(red, gl, head_grads):
         head_grads[ti][j] = v
 
 
-def run_towers(cfg: TowerCfg, table, xs, params, reduce_group=None, reduce: bool = False):
+def run_towers(cfg: TowerCfg, table, xs, params, reduce_group=None, reduce: bool = False, emb=None):
     """reduce: sum the gradients across the data-parallel reduce_group's ranks during the
-    backward (dist.OverlapReducer); ignored unless that group spans more than one rank."""
+    backward (dist.OverlapReducer); ignored unless that group spans more than one rank.
+    emb: the trainable EmbeddingTable whose compute copy `table` is (token-id inputs), or
+    None; its weight then receives a sparse gradient."""
     if cfg.H % 8:
         raise ValueError(f"GRU hidden size {cfg.H} must be a multiple of 8 on the HIP path "
                          "(the step epilogues update 8 consecutive units per thread)")
     group = (reduce_group,) if reduce and dist.active(reduce_group) else None
+    grad_on = torch.is_grad_enabled()
+    emb_w = emb.weight if emb is not None and grad_on and emb.weight.requires_grad else None
+    if emb_w is not None and dist.rank_world(reduce_group)[1] > 1:
+        raise _lib.TTError("a trainable EmbeddingTable is not supported under data parallelism yet (the ranks' "
+                           "sparse row gradients are not gathered): freeze it (trainable=False) or train on one rank")
     # inference (no gradient wanted): the packed compute copies may be reused while the
     # parameters are unchanged (retrieval / serving encode many batches per weight version)
-    cache_ok = not (torch.is_grad_enabled() and any(p.requires_grad for p in params))
-    if cache_ok and cfg.drop_p == 0.0:
+    cache_ok = not (grad_on and any(p.requires_grad for p in params))
+    # a gradient is also wanted by float inputs that require grad and by a trainable table
+    input_grad = emb_w is not None or (grad_on and any(x.requires_grad for x in xs))
+    if cache_ok and cfg.drop_p == 0.0 and not input_grad:
         # ... and nothing of the forward is kept for a backward: the inference kernels (a
         # no-grad call of a model in train() mode still draws dropout, so it stays below)
         return towers_infer(cfg, table, xs, params)
+    if emb_w is not None:
+        return TowersFn.apply(cfg, table, group, cache_ok, *xs, *params, emb_w)
     return TowersFn.apply(cfg, table, group, cache_ok, *xs, *params)

@@ -45,7 +45,7 @@ const char* tt_last_error(void);
  * gru_step_ring, gru_yprev (read by the callers of tt_gru_fwd_yprev, not by the kernels:
  * whether the training step uses the previous-state layout where it is supported); GEMM: gemm_persist, gemm_persist_maxk, gemm_a3, gemm_buf, gemm_bres,
  * bres_rows, bres_form, wgrad_tall, gemm_iepi, gemm_order, gemm_skew, gemm_regstage, gemm_stream_out; losses:
- * hn_gemm, hn_map, hn_scan_gemm, infonce_flash; diagnostics gru_xc_skip, gru_xc_spins. The authoritative list with
+ * hn_gemm, hn_map, hn_scan_gemm, infonce_flash; search: rank_gemm, search_i8_qb; diagnostics gru_xc_skip, gru_xc_spins. The authoritative list with
  * defaults is kOpts in two_towers_amd/csrc/tt_gemm.hip. Every variant computes the same
  * function; they exist for A/B measurement and for tests that compare variants.
  * Not synchronised with launches in flight: set them between steps. */
@@ -423,6 +423,51 @@ long tt_hardneg_ws_size(int dtype, long bq, long nd, int h, int k);
 int tt_search_topk(int dtype, const float* qn, long Q, const void* dn, long N, int h, int k,
                    int32_t* idx, float* val, void* ws, void* stream);
 long tt_search_ws_size(int dtype, long Q, long N, int h, int k);
+
+/* Int8 document index: one byte per component and one fp32 scale per row.
+ *
+ * tt_quantize_rows_i8: symmetric per-row quantisation of x [rows, cols] fp32 (leading
+ * dimension ld) into codes [rows, cols] int8 (dense) and scale [rows] fp32:
+ *   amax = max_c |x[r][c]|;  inv = 127.0f / amax (fp32 division);
+ *   codes[r][c] = clamp((int)rintf(x[r][c] * inv), -127, 127)  (fp32 multiply, round half
+ *   to even);  scale[r] = amax / 127.0f.
+ * A row with amax == 0 gets zero codes and scale 0. cols % 16 == 0, cols <= 1024, ld % 4 == 0,
+ * x and codes 16-byte aligned. NaN / infinity inputs are unspecified; rows = 0 is a no-op.
+ * One wave per row, one pass. */
+int tt_quantize_rows_i8(const float* x, long rows, int cols, long ld, int8_t* codes, float* scale, void* stream);
+
+/* Top-k of every query over an int8 index: qc [Q, h] / qs [Q] the query codes and scales,
+ * dc [N, h] / ds [N] the documents' (resident). The score of (query i, document j) is
+ *   ((float)dot_ij * ds[j]) * qs[i]
+ * with dot_ij the exact int32 dot product of the two code rows and both multiplies fp32, in
+ * that order. (float)dot is exact because |dot| <= 127^2 h <= 16 516 096 < 2^24 for
+ * h <= 1024: that is why h is capped at 1024. h % 16 == 0, code matrices 16-byte aligned,
+ * 1 <= k <= min(tt_topk_max(), N); Q and N limits, ordering (value descending, ties towards
+ * the lower document index) and idx / val as tt_search_topk. ws: tt_search_i8_ws_size bytes;
+ * nothing depends on its previous contents.
+ * k <= 16, few queries: a fused scan (v_dot4_i32_i8, per-lane top-k, no score matrix). By
+ *   measurement one pass of it beats the score block and a second pass does not, so by default
+ *   it runs for Q <= 4 (k <= 4) and Q <= 2 (k <= 16); option search_i8_qb = n > 0 scans up to
+ *   64 queries in groups of at most n, -1 never scans;
+ * k <= 16, more queries: an int8 MFMA kernel (v_mfma_i32_32x32x32_i8; a K tail reads as zero
+ *   codes) writes the fp32 score block [Q, N] into ws, then the column-split top-k;
+ * k > 16, any Q: the same score block, then tt_topk_rows.
+ * Every score is an exact integer times two scales, so all three forms return identical
+ * bits: a k <= 16 answer is a prefix of any larger-k answer at EVERY Q, and a query's row
+ * does not depend on which other queries share the call or on the option (tt_search_topk can
+ * promise the prefix only for Q > 64). tt_search_i8_ws_size follows the option's value at
+ * the time of the call. */
+int tt_search_topk_i8(const int8_t* qc, const float* qs, long Q, const int8_t* dc, const float* ds, long N,
+                      int h, int k, int32_t* idx, float* val, void* ws, void* stream);
+long tt_search_i8_ws_size(long Q, long N, int h, int k);
+
+/* Second stage of a rescored search, the exact scores of a shortlist:
+ *   out[i][r] = qn[i] . dn[cand[i][r]]   (fp32 accumulation),
+ * qn [Q, h] fp32, dn [N, h] in dtype (fp32 or bf16), cand [Q, R] int32, out [Q, R] fp32: R
+ * rows of dn per query instead of N. A candidate outside [0, N) scores -FLT_MAX.
+ * h % 8 == 0, 1 <= R <= 1024, qn and dn 16-byte aligned. One wave per (query, candidate). */
+int tt_gather_scores(int dtype, const float* qn, long Q, const void* dn, long N, int h, const int32_t* cand,
+                     int R, float* out, void* stream);
 
 /* Largest k of tt_topk_rows, tt_search_topk and tt_hardneg_topk: 1024. */
 int tt_topk_max(void);

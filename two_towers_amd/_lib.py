@@ -177,6 +177,12 @@ _SIGS = {
     "tt_search_topk": (c_int, [c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p,
                                c_void_p, c_void_p]),
     "tt_search_ws_size": (c_long, [c_int, c_long, c_long, c_int, c_int]),
+    "tt_quantize_rows_i8": (c_int, [c_void_p, c_long, c_int, c_long, c_void_p, c_void_p, c_void_p]),
+    "tt_search_topk_i8": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_long, c_int, c_int, c_void_p,
+                                  c_void_p, c_void_p, c_void_p]),
+    "tt_search_i8_ws_size": (c_long, [c_long, c_long, c_int, c_int]),
+    "tt_gather_scores": (c_int, [c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_void_p, c_int, c_void_p,
+                                 c_void_p]),
     "tt_topk_max": (c_int, []),
     "tt_topk_rows": (c_int, [c_void_p, c_long, c_long, c_long, c_long, c_int, c_void_p, c_void_p, c_void_p,
                              c_void_p]),

@@ -55,6 +55,9 @@ enum Opt {
   OPT_GRU_YPREV,        // 1: the training step stores the GRU layer outputs in the previous-state layout
                         // (tt_gru_fwd_yprev) where tt_gru_yprev_supported, so dW_hh is a plain TN GEMM; 0: Y as h_t
   OPT_RANK_GEMM,        // 1: full-rank counts through tt_gemm + a pass over the stored rows, no scan
+  OPT_SEARCH_I8_QB,     // int8 search, k <= 16. 0 (default, measured): the fused scan where one pass holds the
+                        // queries (Q <= 4 at k <= 4, Q <= 2 at k <= 16), else the score block; n > 0: the scan up
+                        // to 64 queries, at most n (1, 2, 4, 8; 2 with k > 4) per pass; -1: never the scan
   OPT_N
 };
 int opt(Opt o);

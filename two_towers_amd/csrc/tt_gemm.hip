@@ -46,6 +46,7 @@ constexpr OptDef kOpts[OPT_N] = {
     {"hn_scan_v", "TT_HN_SCAN_V", 5},             {"gemm_w4", "TT_GEMM_W4", 0},
     {"bres_form", "TT_BRES_FORM", 1},             {"wgrad_tall", "TT_WGRAD_TALL", 1},
     {"gru_yprev", "TT_GRU_YPREV", 1},             {"rank_gemm", "TT_RANK_GEMM", 0},
+    {"search_i8_qb", "TT_SEARCH_I8_QB", 0},
 };
 struct OptTable {
   std::atomic<int> v[OPT_N];

@@ -187,3 +187,72 @@ def l2norm_bwd(dy: torch.Tensor, y32: torch.Tensor, norm: torch.Tensor, eps: flo
     call("tt_l2norm_bwd", dy.data_ptr(), y32.data_ptr(), norm.data_ptr(), rows, cols, eps, dx.data_ptr(),
          int(accumulate), stream_ptr(dy.device))
     return dx
+
+
+# ------------------------------------------------------------------ int8 index
+def quantize_rows_i8(x: torch.Tensor):
+    """Symmetric per-row int8 codes of fp32 rows (tt_quantize_rows_i8): (codes int8 [rows,
+    cols], scale fp32 [rows]) with codes = clamp(round(x * (127 / amax)), -127, 127) and
+    scale = amax / 127 per row. x may be a column slice of a wider matrix (row stride a
+    multiple of 4)."""
+    _lib.require_gpu(x)
+    if x.dtype != torch.float32 or x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise _lib.TTError("quantize_rows_i8: x must be fp32 [rows, cols] with unit column stride")
+    rows, cols = x.shape
+    ld = x.stride(0) if rows > 1 else max(x.stride(0), cols)
+    if cols % 16 or not 0 < cols <= 1024:
+        raise _lib.TTError(f"quantize_rows_i8: cols={cols} must be a multiple of 16 and at most 1024")
+    if ld < cols or ld % 4 or x.data_ptr() % 16:
+        raise _lib.TTError(f"quantize_rows_i8: row stride {ld} must be a multiple of 4 (>= cols) and x 16-byte aligned")
+    codes = torch.empty(rows, cols, dtype=torch.int8, device=x.device)
+    scale = torch.empty(rows, dtype=torch.float32, device=x.device)
+    call("tt_quantize_rows_i8", x.data_ptr(), rows, cols, ld, codes.data_ptr(), scale.data_ptr(), stream_ptr(x.device))
+    return codes, scale
+
+
+def search_topk_i8(qc: torch.Tensor, qs: torch.Tensor, dc: torch.Tensor, ds: torch.Tensor, k: int):
+    """Top-k of every query over an int8 index (tt_search_topk_i8): (idx int32 [Q, k], val fp32
+    [Q, k]), val = ((float)dot * ds) * qs. The queries go in chunks so that a stored score
+    block stays within 1 GiB (k > 16) / 4 GiB (k <= 16)."""
+    _lib.require_gpu(qc, qs, dc, ds)
+    for c, s, what in ((qc, qs, "query"), (dc, ds, "document")):
+        if c.dtype != torch.int8 or c.dim() != 2 or not c.is_contiguous():
+            raise _lib.TTError(f"search_topk_i8: {what} codes must be a contiguous int8 matrix")
+        if s.dtype != torch.float32 or not s.is_contiguous() or s.numel() != c.shape[0]:
+            raise _lib.TTError(f"search_topk_i8: {what} scales must be fp32 [{c.shape[0]}]")
+    if qc.shape[1] != dc.shape[1]:
+        raise _lib.TTError(f"search_topk_i8: query width {qc.shape[1]} != document width {dc.shape[1]}")
+    lib = _lib.load()
+    (Q, h), nd = qc.shape, dc.shape[0]
+    idx = torch.empty(Q, k, dtype=torch.int32, device=qc.device)
+    val = torch.empty(Q, k, dtype=torch.float32, device=qc.device)
+    if k > 16:
+        step = max(1, min(Q, (1 << 28) // max(nd, 1)))
+    else:
+        step = max(1, min(Q, (1 << 30) // max(nd, 1)))
+    for r0 in range(0, Q, max(step, 1)):
+        r1 = min(Q, r0 + step)
+        ws = torch.empty(max(lib.tt_search_i8_ws_size(r1 - r0, nd, h, k), 1), dtype=torch.uint8, device=qc.device)
+        call("tt_search_topk_i8", qc[r0:r1].data_ptr(), qs[r0:r1].data_ptr(), r1 - r0, dc.data_ptr(), ds.data_ptr(), nd,
+             h, k, idx[r0:r1].data_ptr(), val[r0:r1].data_ptr(), ws.data_ptr(), stream_ptr(qc.device))
+    return idx, val
+
+
+def gather_scores(qn: torch.Tensor, dn: torch.Tensor, cand: torch.Tensor) -> torch.Tensor:
+    """out[i, r] = qn[i] . dn[cand[i, r]] in fp32 (tt_gather_scores): qn fp32 [Q, h], dn [N, h]
+    fp32 or bf16, cand int32 [Q, R] with 1 <= R <= 1024; a candidate outside [0, N) scores
+    -FLT_MAX."""
+    _lib.require_gpu(qn, dn, cand)
+    if qn.dtype != torch.float32 or qn.dim() != 2 or not qn.is_contiguous():
+        raise _lib.TTError("gather_scores: qn must be a contiguous fp32 matrix")
+    if dn.dim() != 2 or not dn.is_contiguous() or dn.shape[1] != qn.shape[1]:
+        raise _lib.TTError(f"gather_scores: dn must be contiguous [N, {qn.shape[1]}]")
+    if cand.dtype != torch.int32 or cand.dim() != 2 or not cand.is_contiguous() or cand.shape[0] != qn.shape[0]:
+        raise _lib.TTError(f"gather_scores: cand must be contiguous int32 [{qn.shape[0]}, R]")
+    (Q, h), R = qn.shape, cand.shape[1]
+    if h % 8 or not 1 <= R <= _lib.topk_max():
+        raise _lib.TTError(f"gather_scores: h={h} must be a multiple of 8 and 1 <= R={R} <= {_lib.topk_max()}")
+    out = torch.empty(Q, R, dtype=torch.float32, device=qn.device)
+    call("tt_gather_scores", dtype_code(dn.dtype), qn.data_ptr(), Q, dn.data_ptr(), dn.shape[0], h, cand.data_ptr(), R,
+         out.data_ptr(), stream_ptr(qn.device))
+    return out

@@ -49,7 +49,19 @@ def encode_texts(model, texts: Sequence[str], vocab, kind: str, max_length: int 
 
 @torch.no_grad()
 def topk_cosine(query_vecs: torch.Tensor, doc_vecs: torch.Tensor, k: int = 10, compute_dtype=torch.float32):
-    """Top-k documents per query by cosine similarity: (indices int64 [Q,k], scores [Q,k])."""
+    """Top-k documents per query by cosine similarity: (indices int64 [Q,k], scores [Q,k]).
+    compute_dtype=torch.int8: both sides are normalised (eps 1e-8), quantised row by row
+    (ops.quantize_rows_i8) and searched with tt_search_topk_i8; the scores are the int8
+    approximation of the cosines (no rescoring)."""
+    if compute_dtype == torch.int8:
+        _lib.require_gpu(query_vecs, doc_vecs)
+        kmax, nd = _lib.topk_max(), doc_vecs.shape[0]
+        if not 1 <= k <= min(kmax, nd):
+            raise ValueError(f"k={k} needs 1 <= k <= min({kmax}, {nd} documents)")
+        qn, _, _ = ops.l2norm_fwd(query_vecs.float().contiguous(), 1e-8, torch.float32)
+        dn, _, _ = ops.l2norm_fwd(doc_vecs.float().contiguous(), 1e-8, torch.float32)
+        idx, val = ops.search_topk_i8(*ops.quantize_rows_i8(qn), *ops.quantize_rows_i8(dn), k)
+        return idx.long(), val
     idx, val = mine_hard_negatives(query_vecs, doc_vecs, label_offset=-1, k=k, compute_dtype=compute_dtype,
                                    return_values=True)
     return idx.long(), val

@@ -361,7 +361,10 @@ long tt_infonce_fwd_ws_size(long bq, long nd);
 /* Gradient of g * sum_i row_loss[i]: dqn [bq,h], ddn [nd,h] (fp32, overwritten).
  * gscale: DEVICE pointer to the fp32 upstream gradient g (autograd's grad_output, read
  * by the kernels so the backward never waits on the host), or NULL for g = 1.
- * ws: tt_infonce_bwd_ws_size bytes. */
+ * ws: tt_infonce_bwd_ws_size bytes; nothing depends on its previous contents.
+ * As tt_infonce_fwd, a row of qn / dn must be a multiple of 16 bytes (h % 4 == 0 in fp32,
+ * h % 8 == 0 in bf16): any other h, labels outside [0, nd) and (for bq > 0) a null ws are
+ * TT_EINVAL before anything is launched. bq = 0 is a no-op. */
 int tt_infonce_bwd(int dtype, const void* qn, long bq, const void* dn, long nd, int h,
                    float inv_tau, float offdiag_sub, long label_offset, const float* lse,
                    const float* gscale, float* dqn, float* ddn, void* ws, void* stream);

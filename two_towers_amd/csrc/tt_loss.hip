@@ -997,7 +997,11 @@ extern "C" int tt_infonce_bwd(int dtype, const void* qn, long bq, const void* dn
                               float* ddn, void* ws, void* stream) {
   TT_CHECK_ARG(dtype == TT_DT_F32 || dtype == TT_DT_BF16, "tt_infonce_bwd: bad dtype");
   TT_CHECK_ARG(label_offset >= 0 && label_offset + bq <= nd, "tt_infonce_bwd: labels outside [0, nd)");
+  // both paths read whole 16-byte chunks of the operand rows, and the materialised path's
+  // tt_gemm would reject the leading dimension only after infonce_dscore_kernel has run
+  TT_CHECK_ARG(h > 0 && (h * esize(dtype)) % 16 == 0, "tt_infonce_bwd: h=%d misaligned", h);
   if (bq == 0) return 0;
+  TT_CHECK_ARG(ws != nullptr, "tt_infonce_bwd: null workspace");
   hipStream_t st = (hipStream_t)stream;
   if (use_flash(dtype, h)) {
     TT_CHECK_ARG((((uintptr_t)qn | (uintptr_t)dn) & 15) == 0, "tt_infonce_bwd: bf16 rows must be 16-byte aligned");

@@ -552,6 +552,26 @@ int tt_rank_count(int dtype, const void* qn, long Q, const void* dn, long N, int
                   void* stream);
 long tt_rank_count_ws_size(int dtype, long Q, long N, int h);
 
+/* Geometry of the streamed score scan (tt_score.hip hn_scan_kernel), host only: nothing is
+ * launched and no device memory is touched. Reports what tt_hardneg_topk (what = 0; k as in
+ * that call) or tt_rank_count (what = 1; k ignored) would plan for [bq, h] x [nd, h] with the
+ * options now in force, from the very functions the launches use:
+ *   scan     0 the call does not take the streamed path (other dtype / h, k > 16, option
+ *            hn_gemm or rank_gemm, an empty operand): every other field is 0;
+ *            1 hn_scan_kernel runs; 2 (what 0, option hn_scan_gemm) the chunk maxima come from
+ *            the persistent GEMM instead, the other fields are the plan it shares
+ *   variant  hn_scan_v after the fallbacks (0, 4 or 5; 0 for h != 256 and for counts)
+ *   rows     query rows per workgroup
+ *   map      block map after the map 2 fallback (0, 1 or 2)
+ *   nch      64-column tiles of nd;  rt  row tiles;  s  column splits (grid = rt * s)
+ *   tps      tiles per split;  last  tiles of the last split (1 <= last <= tps)
+ * Tests assert it so that a case written for a tile count keeps reaching it. */
+typedef struct tt_scan_geom {
+  int scan, variant, rows, map;
+  long nch, rt, s, tps, last;
+} tt_scan_geom;
+int tt_scan_geometry(int what, int dtype, long bq, long nd, int h, int k, tt_scan_geom* out);
+
 /* MarginRankingLoss with explicit negatives (enhanced_two_tower.py:102-121) on
  * normalised vectors: pos_i = qn_i.dn_{label_offset+i}, negm_i = mean_j qn_i.dn_{idx[i,j]},
  * row_loss_i = max(margin - pos_i + negm_i, 0). Negatives are rows of dn. */

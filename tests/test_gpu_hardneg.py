@@ -47,8 +47,10 @@ CASES = [  # B, nd, h, label_offset, k
     (257, 2000, 128, -1, 16),    # nothing masked (serving), k = 16
     (100, 200, 256, 0, 5),       # nch = 4 < k: every chunk selected
     (40, 70, 128, 3, 1),         # k = 1, two chunks
-    (300, 1000, 512, 0, 5),      # h 512 (configs[4]): 4-wave scan, 2-slot ring
-    (129, 4100, 512, 7, 16),     # h 512: partial row tile, odd tile count per split, k = 16
+    (300, 1000, 512, 0, 5),      # h 512 (configs[4]): 4-wave scan; one tile per workgroup, the ring does not turn
+    (129, 4100, 512, 7, 16),     # h 512: partial row tile, 65 splits of one tile each (RT 2, tps 1), k = 16
+    # every case above plans ONE tile per workgroup (tt_scan_geometry: tps 1); the tile loop at
+    # 2 to 8 tiles per workgroup is tests/test_gpu_scan_ref.py's
     (96, 640, 64, 0, 5),         # GEMM + split path (h = 64)
     (33, 999, 96, -1, 7),        # GEMM + split path (h = 96)
 ]
@@ -169,7 +171,9 @@ def test_hardneg_scan_variants_match(B, nd, lab):
     LDS; 4 64 queries per wave) under each block map: the same MFMA sequence per score, so the
     chunk maxima (masked positive and tail columns included) and the top-k are bit-identical.
     Shapes: the bench's 8192^2, the configs[3] per-rank pool (8192 x 65,536, labels at the
-    rank's offset), ragged row tiles, partial chunks, fewer tiles than the ring's depth."""
+    rank's offset), ragged row tiles, partial chunks. The two large shapes run 8 to 128 tiles
+    per workgroup (even counts, equal splits); the three small ones plan one tile per workgroup,
+    so no ring turns there (odd and short tile counts: tests/test_gpu_scan_ref.py)."""
     g = torch.Generator().manual_seed(B + nd + lab)
     q = torch.nn.functional.normalize(torch.randn(B, 256, generator=g), dim=1)
     d = torch.nn.functional.normalize(torch.randn(nd, 256, generator=g), dim=1)

@@ -106,7 +106,7 @@ def check_exact(q, d, relevant, dt, **kw):
 CASES = [  # Q, N, h
     (300, 1000, 256),    # partial last tile
     (513, 513, 256),     # one row past a 512-row workgroup; Q = N
-    (129, 4100, 512),    # 4-wave scan, odd tile count
+    (129, 4100, 512),    # 4-wave scan, 65 splits of one tile each (RT 2, tps 1)
     (40, 70, 128),       # two chunks
     (96, 640, 64),       # stored path
     (33, 999, 96),       # stored path

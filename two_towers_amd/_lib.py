@@ -111,6 +111,13 @@ class Head1BwdIO(ctypes.Structure):
     ]
 
 
+class ScanGeom(ctypes.Structure):  # include/tt_hip.h tt_scan_geom
+    _fields_ = [
+        ("scan", c_int), ("variant", c_int), ("rows", c_int), ("map", c_int),
+        ("nch", c_long), ("rt", c_long), ("s", c_long), ("tps", c_long), ("last", c_long),
+    ]
+
+
 # name -> (restype, argtypes). Kept in the order of include/tt_hip.h.
 _SIGS = {
     "tt_version": (ctypes.c_char_p, []),
@@ -193,6 +200,7 @@ _SIGS = {
     "tt_rank_count": (c_int, [c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_long, c_void_p, c_void_p, c_void_p,
                               c_int, c_void_p, c_void_p]),
     "tt_rank_count_ws_size": (c_long, [c_int, c_long, c_long, c_int]),
+    "tt_scan_geometry": (c_int, [c_int, c_int, c_long, c_long, c_int, c_int, POINTER(ScanGeom)]),
     "tt_margin_fwd": (c_int, [c_void_p, c_long, c_void_p, c_long, c_int, c_long, c_void_p, c_int, c_float,
                               c_void_p, c_void_p]),
     "tt_margin_bwd": (c_int, [c_void_p, c_long, c_void_p, c_long, c_int, c_long, c_void_p, c_int, c_float,

@@ -715,24 +715,50 @@ HnPlan hn_plan(long bq, long nd, int k, int rows, long tpsm = SC_TPS_MAX) {
   return p;
 }
 
+// The block map a launch of plan p uses: option hn_map, map 2 only where the grid divides.
+int hn_map_for(const HnPlan& p) {
+  int map = tt::opt(tt::OPT_HN_MAP);
+  if (map == 2 && (p.RT % 2 != 0 || p.S % 4 != 0)) map = 0;
+  return map;
+}
+
 template <int KS, int V>
 void hn_scan_launch(const bf16_t* qn, long bq, const bf16_t* dn, long nd, long label_offset, const HnPlan& p, float* CM,
                     hipStream_t st) {
-  int map = tt::opt(tt::OPT_HN_MAP);
-  if (map == 2 && (p.RT % 2 != 0 || p.S % 4 != 0)) map = 0;
   hipLaunchKernelGGL((hn_scan_kernel<KS, V>), dim3((unsigned)(p.RT * p.S)), dim3(ScanCfg<KS, V>::WAVES * 64), 0, st, qn,
-                     bq, dn, nd, label_offset, (int)p.S, (int)p.tps, p.nch, CM, map, RankIn{});
+                     bq, dn, nd, label_offset, (int)p.S, (int)p.tps, p.nch, CM, hn_map_for(p), RankIn{});
+}
+
+// What a scan would run: the variant after the fallbacks, its rows per workgroup and plan.
+// hn_run and rank_scan_run launch from it and tt_scan_geometry reports it.
+struct HnGeom {
+  int v, rows;
+  HnPlan p;
+};
+
+template <int KS>
+HnGeom hn_geom(long bq, long nd, int k) {
+  int v = KS == 8 ? tt::opt(tt::OPT_HN_SCAN_V) : 0;
+  if (v != 4 && v != 5) v = 0;
+  if (v == 5 && bq * ((nd + SC_COLS - 1) / SC_COLS) * 4 >= (1L << 31)) v = 0;  // CM offsets in 32 bits
+  if (v == 4) return {v, ScanCfg<KS, 4>::ROWS, hn_plan(bq, nd, k, ScanCfg<KS, 4>::ROWS, ScanCfg<KS, 4>::PLAN_TPS)};
+  if (v == 5) return {v, ScanCfg<KS, 5>::ROWS, hn_plan(bq, nd, k, ScanCfg<KS, 5>::ROWS, ScanCfg<KS, 5>::PLAN_TPS)};
+  return {v, ScanCfg<KS>::ROWS, hn_plan(bq, nd, k, ScanCfg<KS>::ROWS)};
+}
+
+// a count needs no per-tile staging, so a split may hold any number of tiles: as many
+// splits as fill the 256 CUs, no more
+template <int KS>
+HnGeom rank_geom(long bq, long nd) {
+  return {0, ScanCfg<KS>::ROWS, hn_plan(bq, nd, 1, ScanCfg<KS>::ROWS, 1L << 30)};
 }
 
 template <int KS>
 int hn_run(const bf16_t* qn, long bq, const bf16_t* dn, long nd, long label_offset, int k, int32_t* idx, float* val,
            char* ws, hipStream_t st) {
-  int v = KS == 8 ? tt::opt(tt::OPT_HN_SCAN_V) : 0;
-  if (v != 4 && v != 5) v = 0;
-  if (v == 5 && bq * ((nd + SC_COLS - 1) / SC_COLS) * 4 >= (1L << 31)) v = 0;  // CM offsets in 32 bits
-  const HnPlan p = v == 4   ? hn_plan(bq, nd, k, ScanCfg<KS, 4>::ROWS, ScanCfg<KS, 4>::PLAN_TPS)
-                   : v == 5 ? hn_plan(bq, nd, k, ScanCfg<KS, 5>::ROWS, ScanCfg<KS, 5>::PLAN_TPS)
-                            : hn_plan(bq, nd, k, ScanCfg<KS>::ROWS);
+  const HnGeom geo = hn_geom<KS>(bq, nd, k);
+  const int v = geo.v;
+  const HnPlan& p = geo.p;
   float* CM = reinterpret_cast<float*>(ws);
   int32_t* sel = reinterpret_cast<int32_t*>(ws + p.off_sel);
   float* cand = reinterpret_cast<float*>(ws + p.off_cand);
@@ -866,11 +892,8 @@ __global__ __launch_bounds__(256) void rank_count_rows_kernel(const float* __res
 template <int KS>
 int rank_scan_run(const bf16_t* qn, long bq, const bf16_t* dn, long nd, long col_offset, const float* theta,
                   const int32_t* tcol, int32_t* count, hipStream_t st) {
-  // a count needs no per-tile staging, so a split may hold any number of tiles: as many
-  // splits as fill the 256 CUs, no more
-  const HnPlan p = hn_plan(bq, nd, 1, ScanCfg<KS>::ROWS, 1L << 30);
-  int map = tt::opt(tt::OPT_HN_MAP);
-  if (map == 2 && (p.RT % 2 != 0 || p.S % 4 != 0)) map = 0;
+  const HnPlan p = rank_geom<KS>(bq, nd).p;
+  const int map = hn_map_for(p);
   hipLaunchKernelGGL((hn_scan_kernel<KS, 0, 1>), dim3((unsigned)(p.RT * p.S)), dim3(ScanCfg<KS>::WAVES * 64), 0, st, qn,
                      bq, dn, nd, col_offset, (int)p.S, (int)p.tps, p.nch, reinterpret_cast<float*>(count), map,
                      RankIn{theta, tcol});
@@ -911,6 +934,35 @@ int tt_hn_scan_topk(const void* qn, long bq, const void* dn, long nd, int h, lon
   if (h == 512) return hn_run<16>(q, bq, d, nd, label_offset, k, idx, val, w, st);
   if (h == 256) return hn_run<8>(q, bq, d, nd, label_offset, k, idx, val, w, st);
   return hn_run<4>(q, bq, d, nd, label_offset, k, idx, val, w, st);
+}
+
+// ---------------------------------------------------------------- geometry report
+// Host only, nothing is launched: what tt_hardneg_topk (what 0) or tt_rank_count (what 1)
+// would plan with the options now in force. Filled from hn_geom / rank_geom / hn_map_for, the
+// functions the launches themselves use.
+extern "C" int tt_scan_geometry(int what, int dtype, long bq, long nd, int h, int k, tt_scan_geom* out) {
+  TT_CHECK_ARG(out != nullptr, "tt_scan_geometry: null out");
+  TT_CHECK_ARG(what == 0 || what == 1, "tt_scan_geometry: what=%d (0 hard negatives, 1 rank count)", what);
+  *out = tt_scan_geom{};
+  if (bq <= 0 || nd <= 0) return 0;
+  HnGeom g;
+  if (what == 0) {  // tt_hardneg_topk sends k > 16 and the other shapes to the stored paths
+    if (k < 1 || k > ttk::SK_MAX || !tt_hn_scan_supported(dtype, h)) return 0;
+    g = h == 512 ? hn_geom<16>(bq, nd, k) : h == 256 ? hn_geom<8>(bq, nd, k) : hn_geom<4>(bq, nd, k);
+  } else {
+    if (!rank_fused(dtype, h)) return 0;
+    g = h == 512 ? rank_geom<16>(bq, nd) : h == 256 ? rank_geom<8>(bq, nd) : rank_geom<4>(bq, nd);
+  }
+  out->scan = what == 0 && tt::opt(tt::OPT_HN_SCAN_GEMM) ? 2 : 1;
+  out->variant = g.v;
+  out->rows = g.rows;
+  out->map = hn_map_for(g.p);
+  out->nch = g.p.nch;
+  out->rt = g.p.RT;
+  out->s = g.p.S;
+  out->tps = g.p.tps;
+  out->last = g.p.nch - (g.p.S - 1) * g.p.tps;
+  return 0;
 }
 
 // ---------------------------------------------------------------- full ranks: C ABI

@@ -420,6 +420,49 @@ int tt_infonce_sym_bwd(int dtype, const void* qn, const void* dn, long n, int h,
                        float* dqn, float* ddn, void* ws, void* stream);
 long tt_infonce_sym_bwd_ws_size(int dtype, long n, int h);
 
+/* Group masks: in-batch false negatives. Rows carry row_group[i] and columns col_group[j]
+ * (device int32, [bq] and [nd]). THE GROUP RULE, the same in every entry point below:
+ *   column j is EXCLUDED for row i  iff
+ *     j != label_offset + i  and  row_group[i] >= 0  and  col_group[j] == row_group[i].
+ * A negative id is "no group" and excludes nothing; the label column is never excluded.
+ * In the softmax losses an excluded entry is absent: it adds nothing to the log-sum-exp,
+ * dS_ij = 0, and offdiag_sub does not matter for it. The symmetric loss takes one vector
+ * group[n] for both sides (label_offset 0: excl(i, j) iff i != j, group[i] >= 0 and
+ * group[i] == group[j]); the same entries are absent from the column LSE.
+ * The *_grp entry points are the ungrouped ones with the ids added: the same argument
+ * checks before anything is launched, the same workspaces (the same *_ws_size functions,
+ * nothing depends on their previous contents), the same kernels with the rule compiled
+ * into their tile epilogues. Both id pointers NULL is the ungrouped call, bit for bit (and
+ * so are ids that are all negative); exactly one NULL is TT_EINVAL. */
+int tt_infonce_fwd_grp(int dtype, const void* qn, long bq, const void* dn, long nd, int h,
+                       float inv_tau, float offdiag_sub, long label_offset, const int32_t* row_group,
+                       const int32_t* col_group, float* lse, float* row_loss, void* ws, void* stream);
+int tt_infonce_bwd_grp(int dtype, const void* qn, long bq, const void* dn, long nd, int h,
+                       float inv_tau, float offdiag_sub, long label_offset, const int32_t* row_group,
+                       const int32_t* col_group, const float* lse, const float* gscale, float* dqn,
+                       float* ddn, void* ws, void* stream);
+int tt_infonce_sym_fwd_grp(int dtype, const void* qn, const void* dn, long n, int h, float inv_tau,
+                           const int32_t* group, float* lse_row, float* lse_col, float* row_loss,
+                           void* ws, void* stream);
+int tt_infonce_sym_bwd_grp(int dtype, const void* qn, const void* dn, long n, int h, float inv_tau,
+                           const int32_t* group, const float* lse_row, const float* lse_col,
+                           const float* gscale, float* dqn, float* ddn, void* ws, void* stream);
+/* Mining under the group rule: idx_in [rows, kin] (val_in [rows, kin] optional) are sorted
+ * candidate lists, e.g. tt_hardneg_topk's answer for kin = k + g, g the largest number of
+ * columns the rule can exclude for one row. Per row the candidates are walked in order and
+ * those the rule does not exclude are kept (a candidate outside [0, nd) is dropped too);
+ * the first k kept go to idx [rows, k] (and val), nkept[row] = min(kept, k). With fewer
+ * than k kept the remaining slots repeat the last kept entry, or column label_offset + row
+ * with value -1 when nothing was kept (column 0 when label_offset < 0), so every index
+ * written is in [0, nd). An excluded column is never returned; the label column keeps the
+ * behaviour of tt_hardneg_topk (it reads as -1 and may be returned once k reaches it).
+ * 1 <= k <= kin; label_offset < 0 or label_offset + rows <= nd; the outputs must not
+ * overlap the inputs. row_group and col_group are both required. One wave per row, ordered
+ * compaction by ballot and prefix count: no atomics. rows = 0 is a no-op. */
+int tt_topk_drop_groups(const int32_t* idx_in, const float* val_in, long rows, int kin, long label_offset,
+                        const int32_t* row_group, const int32_t* col_group, long nd, int k, int32_t* idx,
+                        float* val, int32_t* nkept, void* stream);
+
 /* Hard-negative mining, batched over rows (get_hard_negatives,
  * enhanced_two_tower.py:123-133): sims = qn dn^T (cosine for normalised inputs), the
  * positive column label_offset+i set to -1 (label_offset < 0: no column masked), top-k

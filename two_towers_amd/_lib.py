@@ -179,6 +179,16 @@ _SIGS = {
     "tt_infonce_sym_bwd": (c_int, [c_int, c_void_p, c_void_p, c_long, c_int, c_float, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "tt_infonce_sym_bwd_ws_size": (c_long, [c_int, c_long, c_int]),
+    "tt_infonce_fwd_grp": (c_int, [c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_float, c_float, c_long,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tt_infonce_bwd_grp": (c_int, [c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_float, c_float, c_long,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tt_infonce_sym_fwd_grp": (c_int, [c_int, c_void_p, c_void_p, c_long, c_int, c_float, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tt_infonce_sym_bwd_grp": (c_int, [c_int, c_void_p, c_void_p, c_long, c_int, c_float, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tt_topk_drop_groups": (c_int, [c_void_p, c_void_p, c_long, c_int, c_long, c_void_p, c_void_p, c_long, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "tt_hardneg_topk": (c_int, [c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_long, c_int, c_void_p,
                                 c_void_p, c_void_p, c_void_p]),
     "tt_hardneg_ws_size": (c_long, [c_int, c_long, c_long, c_int, c_int]),

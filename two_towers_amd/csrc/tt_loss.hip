@@ -75,11 +75,18 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict
 // Grid (col_splits, row_blocks). Each workgroup sweeps its share of 128-column
 // dn tiles for 128 q rows, keeping a per-lane running (max, sum-exp) per row, and
 // writes one (max, sumexp) partial per row and split. S is never stored.
-template <typename T>
-__global__ __launch_bounds__(256) void infonce_fwd_kernel(const T* __restrict__ qn, long bq, const T* __restrict__ dn,
+// GRP: the group rule of tt_hip.h. An excluded element takes the col >= nd sentinel, so a
+// split whose whole share of a row is excluded writes the neutral partial (-FLT_MAX, 0).
+// (GRP asks for two waves per SIMD, which the ungrouped code reaches unasked at 181 / 182
+// VGPRs + 64 AGPRs: without the request the grouped instantiation settles at 203 + 64, one
+// wave; with it at 252 in all and no scratch. 1 is the default and leaves GRP = false as is.)
+template <typename T, bool GRP = false>
+__global__ __launch_bounds__(256, GRP ? 2 : 1) void infonce_fwd_kernel(const T* __restrict__ qn, long bq, const T* __restrict__ dn,
                                                           long nd, int h, float inv_tau, float offdiag,
                                                           long label_off, int ct_per_split, float* __restrict__ pm,
-                                                          float* __restrict__ pl, float* __restrict__ diag) {
+                                                          float* __restrict__ pl, float* __restrict__ diag,
+                                                          const int32_t* __restrict__ row_group,
+                                                          const int32_t* __restrict__ col_group) {
   using ML = ttg::MainLoop<T, false, false, 128, 128>;
   __shared__ __attribute__((aligned(16))) char lds[ML::LDS_BYTES];
   __shared__ float red_m[2][128], red_l[2][128];
@@ -95,6 +102,15 @@ __global__ __launch_bounds__(256) void infonce_fwd_kernel(const T* __restrict__ 
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int r = 0; r < 4; ++r) { rm[i][r] = -FLT_MAX; rl[i][r] = 0.f; }
+  // GRP: the ids of the workgroup's rows wait in LDS (-1: none, or row >= bq) and are read
+  // in the tile epilogue: 16 more registers held across the main loop cost the second wave
+  [[maybe_unused]] const int* rg_s = nullptr;
+  if constexpr (GRP) {
+    __shared__ int rg_lds[128];
+    if (threadIdx.x < 128) rg_lds[threadIdx.x] = m0 + threadIdx.x < bq ? row_group[m0 + threadIdx.x] : -1;
+    __syncthreads();
+    rg_s = rg_lds;
+  }
 
   for (long ct = ct0; ct < ct1; ++ct) {
     const int n0 = (int)(ct * 128);
@@ -103,6 +119,14 @@ __global__ __launch_bounds__(256) void infonce_fwd_kernel(const T* __restrict__ 
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    [[maybe_unused]] int cg[4];  // GRP: the ids of this lane's columns of the tile
+    if constexpr (GRP) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const long col = n0 + wn + 16 * j + (lane & 15);
+        cg[j] = col < nd ? col_group[col] : -1;
+      }
+    }
     ML::run(ttg::KCPlain<T>{qn, h, m0, (int)bq}, ttg::KCPlain<T>{dn, h, n0, (int)nd}, h, 0, nk, lds, acc);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -111,6 +135,8 @@ __global__ __launch_bounds__(256) void infonce_fwd_kernel(const T* __restrict__ 
         const long row = m0 + wm + 16 * i + 4 * (lane >> 4) + r;
         float sv[4];
         float tmax = -FLT_MAX;
+        [[maybe_unused]] int rgv = -1;
+        if constexpr (GRP) rgv = rg_s[wm + 16 * i + 4 * (lane >> 4) + r];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const long col = n0 + wn + 16 * j + (lane & 15);
@@ -119,6 +145,8 @@ __global__ __launch_bounds__(256) void infonce_fwd_kernel(const T* __restrict__ 
           if (!lab) s -= offdiag;
           if (lab && row < bq) diag[row] = s;
           if (col >= nd) s = -FLT_MAX;
+          if constexpr (GRP)
+            if (!lab && rgv >= 0 && cg[j] == rgv) s = -FLT_MAX;
           sv[j] = s;
           tmax = fmaxf(tmax, s);
         }
@@ -180,12 +208,17 @@ __global__ __launch_bounds__(256) void infonce_finalize_kernel(const float* __re
 // one barrier per tile). One partial per (row block, column) goes to cpm/cpl [rb][n]; each
 // is written by exactly one workgroup, and infonce_sym_finalize_kernel merges them in
 // ascending block order. Rows >= n never enter a column's sum, columns >= n never a row's.
-template <typename T>
+// GRP: the group rule of tt_hip.h with one id vector for both sides; an excluded element
+// enters neither its row's nor its column's (max, sum-exp): a column none of whose rows in a
+// lane, wave or row block is allowed gives the neutral partial (-FLT_MAX, 0) there. inv_tau
+// must be > 0 (the excluded score is -inf * inv_tau).
+template <typename T, bool GRP = false>
 __global__ __launch_bounds__(256) void infonce_sym_fwd_kernel(const T* __restrict__ qn, const T* __restrict__ dn,
                                                               long n, int h, float inv_tau, int ct_per_split,
                                                               float* __restrict__ pm, float* __restrict__ pl,
                                                               float* __restrict__ cpm, float* __restrict__ cpl,
-                                                              float* __restrict__ diag) {
+                                                              float* __restrict__ diag,
+                                                              const int32_t* __restrict__ group) {
   using ML = ttg::MainLoop<T, false, false, 128, 128>;
   __shared__ __attribute__((aligned(16))) char lds[ML::LDS_BYTES];
   __shared__ float red_m[2][128], red_l[2][128];
@@ -202,6 +235,16 @@ __global__ __launch_bounds__(256) void infonce_sym_fwd_kernel(const T* __restric
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int r = 0; r < 4; ++r) { rm[i][r] = -FLT_MAX; rl[i][r] = 0.f; }
+  [[maybe_unused]] int rg[4][4];  // GRP: the ids of this lane's rows (-1: none, or row >= n)
+  if constexpr (GRP) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const long row = m0 + wm + 16 * i + 4 * (lane >> 4) + r;
+        rg[i][r] = row < n ? group[row] : -1;
+      }
+  }
 
   for (long ct = ct0; ct < ct1; ++ct) {
     const int n0 = (int)(ct * 128);
@@ -211,7 +254,33 @@ __global__ __launch_bounds__(256) void infonce_sym_fwd_kernel(const T* __restric
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    [[maybe_unused]] int cg[4];  // GRP: the ids of this lane's columns of the tile
+    if constexpr (GRP) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const long col = n0 + wn + 16 * j + (lane & 15);
+        cg[j] = col < n ? group[col] : -1;
+      }
+    }
     ML::run(ttg::KCPlain<T>{qn, h, m0, (int)n}, ttg::KCPlain<T>{dn, h, n0, (int)n}, h, 0, nk, lds, acc);
+    // GRP: an excluded score becomes -inf here, on the accumulator, and the epilogue below is
+    // the ungrouped one to the letter: the element then never raises a maximum (a column or
+    // row share that is excluded as a whole keeps -FLT_MAX) and its exp terms are exactly 0.
+    // Masking s inside the epilogue instead changed which s - cm the compiler contracts into
+    // an fma, and with it the last bit of a few column sums even when no id matches.
+    if constexpr (GRP) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const long row = m0 + wm + 16 * i + 4 * (lane >> 4) + r;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const long col = n0 + wn + 16 * j + (lane & 15);
+            if (col != row && rg[i][r] >= 0 && cg[j] == rg[i][r]) acc[i][j][r] = -INFINITY;
+          }
+        }
+    }
     float cm[4], cl[4];  // per column j of this lane: over the 16 rows it holds
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -336,14 +405,17 @@ __global__ __launch_bounds__(256) void infonce_sym_finalize_kernel(const float* 
 // upstream gradient, read on the device: no host sync) or 1 when gscale is null.
 // SYM (square, label_off 0, no offdiag): lse is the row LSE, lse_col the column LSE and
 // dS[i][j] = g/2 * (exp(s - lse[i]) + exp(s - lse_col[j]) - 2 [i == j]).
-template <typename T, bool SYM = false>
+// GRP: the group rule of tt_hip.h (SYM: row_group == col_group); an excluded element is 0.
+template <typename T, bool SYM = false, bool GRP = false>
 __global__ __launch_bounds__(256) void infonce_dscore_kernel(const T* __restrict__ qn, long bq,
                                                              const T* __restrict__ dn, long nd, int h, float inv_tau,
                                                              float offdiag, long label_off,
                                                              const float* __restrict__ lse,
                                                              const float* __restrict__ gscale, long ldds,
                                                              T* __restrict__ ds,
-                                                             const float* __restrict__ lse_col) {
+                                                             const float* __restrict__ lse_col,
+                                                             const int32_t* __restrict__ row_group,
+                                                             const int32_t* __restrict__ col_group) {
   const float gs = gscale ? *gscale : 1.f;
   using ML = ttg::MainLoop<T, false, false, 128, 128>;
   __shared__ __attribute__((aligned(16))) char lds[ML::LDS_BYTES];
@@ -360,6 +432,13 @@ __global__ __launch_bounds__(256) void infonce_dscore_kernel(const T* __restrict
     if (row >= bq || col >= nd) return;
     const bool lab = (col == label_off + row);
     float s = v * inv_tau;
+    if constexpr (GRP) {
+      const int g = row_group[row];
+      if (!lab && g >= 0 && col_group[col] == g) {
+        Elt<T>::st(ds + row * ldds + col, 0.f);
+        return;
+      }
+    }
     if constexpr (SYM) {
       const float p = __expf(s - lse[row]) + __expf(s - lse_col[col]);
       Elt<T>::st(ds + row * ldds + col, 0.5f * gs * (p - (lab ? 2.f : 0.f)));
@@ -432,14 +511,19 @@ TT_DEV void flash_stage(const bf16_t* src, long rows, long r0, int nrows_img, ui
     }
 }
 
-template <int H, bool OWNQ, bool SYM = false>
+// GRP: the group rule of tt_hip.h. The own rows' ids are loaded once next to lown, the swept
+// tile's per tile next to lx (row ids for query rows, column ids for document rows; SYM: one
+// vector); an excluded dS is 0 before the bf16 rounding.
+template <int H, bool OWNQ, bool SYM = false, bool GRP = false>
 __global__ __launch_bounds__(512) void infonce_bwd_flash_kernel(const bf16_t* __restrict__ qn, long bq,
                                                                 const bf16_t* __restrict__ dn, long nd, float inv_tau,
                                                                 float offdiag, long label_off,
                                                                 const float* __restrict__ lse,
                                                                 const float* __restrict__ gscale, int tiles_per_split,
                                                                 float* __restrict__ out,
-                                                                const float* __restrict__ lse_col) {
+                                                                const float* __restrict__ lse_col,
+                                                                const int32_t* __restrict__ row_group,
+                                                                const int32_t* __restrict__ col_group) {
   using C = FlashCfg<H>;
   __shared__ __attribute__((aligned(16))) char lds[C::LDS];
   const float gs = gscale ? *gscale : 1.f;
@@ -472,6 +556,20 @@ __global__ __launch_bounds__(512) void infonce_bwd_flash_kernel(const bf16_t* __
       const long row = o0 + wm + 16 * i + 4 * (lane >> 4) + r;
       lown[i][r] = ((OWNQ || SYM) && row < nown) ? lse_own[row] : 0.f;
     }
+  // GRP: ids of the own rows and, per tile, of the swept rows. Out-of-range rows get ids that
+  // match nothing (-1 on the query side fails g >= 0; -2 on the document side equals no id)
+  [[maybe_unused]] const int32_t* grp_own = OWNQ ? row_group : col_group;
+  [[maybe_unused]] const int32_t* grp_x = OWNQ ? col_group : row_group;
+  [[maybe_unused]] int gown[2][4];
+  if constexpr (GRP) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const long row = o0 + wm + 16 * i + 4 * (lane >> 4) + r;
+        gown[i][r] = row < nown ? grp_own[row] : (OWNQ ? -1 : -2);
+      }
+  }
   if (t0 < t1) {
     flash_stage<H>(O, nown, o0, 128, lb);
     flash_stage<H>(X, nx, t0 * 64, 64, lb + C::OWN);
@@ -511,6 +609,14 @@ __global__ __launch_bounds__(512) void infonce_bwd_flash_kernel(const bf16_t* __
         lx[j] = xr < nx ? lse_x[xr] : 0.f;
       }
     }
+    [[maybe_unused]] int gx[2];
+    if constexpr (GRP) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const long xr = t * 64 + wn + 16 * j + (lane & 15);
+        gx[j] = xr < nx ? grp_x[xr] : (OWNQ ? -2 : -1);
+      }
+    }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -530,6 +636,10 @@ __global__ __launch_bounds__(512) void infonce_bwd_flash_kernel(const bf16_t* __
             if (!lab) s -= offdiag;
             const float p = __expf(s - (OWNQ ? lown[i][r] : lx[j]));
             v = (orow < nown && xrow < nx) ? gs * (p - (lab ? 1.f : 0.f)) : 0.f;
+          }
+          if constexpr (GRP) {
+            const int gq = OWNQ ? gown[i][r] : gx[j], gd = OWNQ ? gx[j] : gown[i][r];
+            if (!lab && gq >= 0 && gd == gq) v = 0.f;
           }
           *reinterpret_cast<bf16_t*>(dsimg + orl * 128 + ((((xcl >> 3) ^ ((orl >> 1) & 7))) << 4) + (xcl & 7) * 2) =
               f2bf(v);
@@ -882,9 +992,14 @@ extern "C" long tt_infonce_fwd_ws_size(long bq, long nd) {
   return (2L * splits * bq + bq) * (long)sizeof(float);
 }
 
-extern "C" int tt_infonce_fwd(int dtype, const void* qn, long bq, const void* dn, long nd, int h, float inv_tau,
-                              float offdiag_sub, long label_offset, float* lse, float* row_loss, void* ws,
-                              void* stream) {
+// exactly one id pointer is an error; both NULL select the ungrouped instantiations
+#define TT_CHECK_GROUPS(a, b, what) \
+  TT_CHECK_ARG(((a) == nullptr) == ((b) == nullptr), what ": row_group and col_group must both be given or both be NULL")
+
+extern "C" int tt_infonce_fwd_grp(int dtype, const void* qn, long bq, const void* dn, long nd, int h, float inv_tau,
+                                  float offdiag_sub, long label_offset, const int32_t* row_group,
+                                  const int32_t* col_group, float* lse, float* row_loss, void* ws, void* stream) {
+  TT_CHECK_GROUPS(row_group, col_group, "tt_infonce_fwd_grp");
   TT_CHECK_ARG(dtype == TT_DT_F32 || dtype == TT_DT_BF16, "tt_infonce_fwd: bad dtype");
   TT_CHECK_ARG(label_offset >= 0 && label_offset + bq <= nd, "tt_infonce_fwd: labels outside [0, nd)");
   TT_CHECK_ARG((h * esize(dtype)) % 16 == 0, "tt_infonce_fwd: h=%d misaligned", h);
@@ -902,17 +1017,28 @@ extern "C" int tt_infonce_fwd(int dtype, const void* qn, long bq, const void* dn
   float* pl = pool + (long)splits * bq;
   float* diag = pl + (long)splits * bq;
   dim3 grid(splits, rb);
-  if (dtype == TT_DT_BF16)
-    hipLaunchKernelGGL(infonce_fwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)qn, bq, (const bf16_t*)dn,
-                       nd, h, inv_tau, offdiag_sub, label_offset, per, pm, pl, diag);
-  else
-    hipLaunchKernelGGL(infonce_fwd_kernel<float>, grid, dim3(256), 0, st, (const float*)qn, bq, (const float*)dn, nd,
-                       h, inv_tau, offdiag_sub, label_offset, per, pm, pl, diag);
+  const bool grp = row_group != nullptr;
+#define TT_LAUNCH_FWD(T, G)                                                                                      \
+  hipLaunchKernelGGL((infonce_fwd_kernel<T, G>), grid, dim3(256), 0, st, (const T*)qn, bq, (const T*)dn, nd, h, \
+                     inv_tau, offdiag_sub, label_offset, per, pm, pl, diag, row_group, col_group)
+  if (dtype == TT_DT_BF16) {
+    if (grp) TT_LAUNCH_FWD(bf16_t, true); else TT_LAUNCH_FWD(bf16_t, false);
+  } else {
+    if (grp) TT_LAUNCH_FWD(float, true); else TT_LAUNCH_FWD(float, false);
+  }
+#undef TT_LAUNCH_FWD
   TT_CHECK_LAUNCH("infonce_fwd_kernel");
   hipLaunchKernelGGL(infonce_finalize_kernel, dim3(tt_ceil_div(bq, 256)), dim3(256), 0, st, pm, pl, splits, bq, diag,
                      lse, row_loss);
   TT_CHECK_LAUNCH("infonce_finalize_kernel");
   return 0;
+}
+
+extern "C" int tt_infonce_fwd(int dtype, const void* qn, long bq, const void* dn, long nd, int h, float inv_tau,
+                              float offdiag_sub, long label_offset, float* lse, float* row_loss, void* ws,
+                              void* stream) {
+  return tt_infonce_fwd_grp(dtype, qn, bq, dn, nd, h, inv_tau, offdiag_sub, label_offset, nullptr, nullptr, lse,
+                            row_loss, ws, stream);
 }
 
 static bool use_flash(int dtype, int h) { return flash_ok(dtype, h) && tt::opt(tt::OPT_INFONCE_FLASH) != 0; }
@@ -931,15 +1057,22 @@ extern "C" long tt_infonce_bwd_ws_size(int dtype, long bq, long nd, int h) {
 template <int H, bool OWNQ, bool SYM = false>
 static int flash_role(const bf16_t* qn, long bq, const bf16_t* dn, long nd, float inv_tau, float offdiag,
                       long label_off, const float* lse, const float* gscale, float* out, float* slab,
-                      hipStream_t st, const float* lse_col = nullptr) {
+                      hipStream_t st, const float* lse_col = nullptr, const int32_t* row_group = nullptr,
+                      const int32_t* col_group = nullptr) {
   const long nown = OWNQ ? bq : nd, nx = OWNQ ? nd : bq;
   const long ntile = (nx + 63) / 64;
   int splits = flash_splits(nown, nx);
   const int per = tt_ceil_div(ntile, splits);
   splits = tt_ceil_div(ntile, per);
   const dim3 grid((unsigned)splits, (unsigned)tt_ceil_div(nown, 128));
-  hipLaunchKernelGGL((infonce_bwd_flash_kernel<H, OWNQ, SYM>), grid, dim3(512), 0, st, qn, bq, dn, nd, inv_tau,
-                     offdiag, label_off, lse, gscale, per, splits > 1 ? slab : out, lse_col);
+  if (row_group)
+    hipLaunchKernelGGL((infonce_bwd_flash_kernel<H, OWNQ, SYM, true>), grid, dim3(512), 0, st, qn, bq, dn, nd,
+                       inv_tau, offdiag, label_off, lse, gscale, per, splits > 1 ? slab : out, lse_col, row_group,
+                       col_group);
+  else
+    hipLaunchKernelGGL((infonce_bwd_flash_kernel<H, OWNQ, SYM, false>), grid, dim3(512), 0, st, qn, bq, dn, nd,
+                       inv_tau, offdiag, label_off, lse, gscale, per, splits > 1 ? slab : out, lse_col, row_group,
+                       col_group);
   TT_CHECK_LAUNCH("infonce_bwd_flash_kernel");
   if (splits > 1) {
     const long n = nown * H;
@@ -955,7 +1088,8 @@ static int flash_role(const bf16_t* qn, long bq, const bf16_t* dn, long nd, floa
 template <bool SYM>
 static int infonce_bwd_materialised(int dtype, const void* qn, long bq, const void* dn, long nd, int h, float inv_tau,
                                     float offdiag_sub, long label_offset, const float* lse, const float* lse_col,
-                                    const float* gscale, float* dqn, float* ddn, void* ws, void* stream) {
+                                    const float* gscale, float* dqn, float* ddn, void* ws, void* stream,
+                                    const int32_t* row_group, const int32_t* col_group) {
   hipStream_t st = (hipStream_t)stream;
   InfoWs w;
   infonce_ws(dtype, bq, nd, h, &w);
@@ -964,14 +1098,17 @@ static int infonce_bwd_materialised(int dtype, const void* qn, long bq, const vo
   float* sk = reinterpret_cast<float*>(base + w.sk);
   const long ldds = (nd + 7) / 8 * 8;  // 16-byte aligned rows for the dS operand
   dim3 grid((unsigned)tt_ceil_div(nd, 128), (unsigned)tt_ceil_div(bq, 128));
-  if (dtype == TT_DT_BF16)
-    hipLaunchKernelGGL((infonce_dscore_kernel<bf16_t, SYM>), grid, dim3(256), 0, st, (const bf16_t*)qn, bq,
-                       (const bf16_t*)dn, nd, h, inv_tau, offdiag_sub, label_offset, lse, gscale, ldds, (bf16_t*)ds,
-                       lse_col);
-  else
-    hipLaunchKernelGGL((infonce_dscore_kernel<float, SYM>), grid, dim3(256), 0, st, (const float*)qn, bq,
-                       (const float*)dn, nd, h, inv_tau, offdiag_sub, label_offset, lse, gscale, ldds, (float*)ds,
-                       lse_col);
+  const bool grp = row_group != nullptr;
+#define TT_LAUNCH_DS(T, G)                                                                                       \
+  hipLaunchKernelGGL((infonce_dscore_kernel<T, SYM, G>), grid, dim3(256), 0, st, (const T*)qn, bq, (const T*)dn, \
+                     nd, h, inv_tau, offdiag_sub, label_offset, lse, gscale, ldds, (T*)ds, lse_col, row_group,   \
+                     col_group)
+  if (dtype == TT_DT_BF16) {
+    if (grp) TT_LAUNCH_DS(bf16_t, true); else TT_LAUNCH_DS(bf16_t, false);
+  } else {
+    if (grp) TT_LAUNCH_DS(float, true); else TT_LAUNCH_DS(float, false);
+  }
+#undef TT_LAUNCH_DS
   TT_CHECK_LAUNCH("infonce_dscore_kernel");
   // dqn = inv_tau * dS dn   (NN)
   {
@@ -992,9 +1129,12 @@ static int infonce_bwd_materialised(int dtype, const void* qn, long bq, const vo
   return 0;
 }
 
-extern "C" int tt_infonce_bwd(int dtype, const void* qn, long bq, const void* dn, long nd, int h, float inv_tau,
-                              float offdiag_sub, long label_offset, const float* lse, const float* gscale, float* dqn,
-                              float* ddn, void* ws, void* stream) {
+extern "C" int tt_infonce_bwd_grp(int dtype, const void* qn, long bq, const void* dn, long nd, int h, float inv_tau,
+                                  float offdiag_sub, long label_offset, const int32_t* row_group,
+                                  const int32_t* col_group, const float* lse, const float* gscale, float* dqn,
+                                  float* ddn, void* ws, void* stream) {
+  const int32_t *rg = row_group, *cg = col_group;
+  TT_CHECK_GROUPS(rg, cg, "tt_infonce_bwd_grp");
   TT_CHECK_ARG(dtype == TT_DT_F32 || dtype == TT_DT_BF16, "tt_infonce_bwd: bad dtype");
   TT_CHECK_ARG(label_offset >= 0 && label_offset + bq <= nd, "tt_infonce_bwd: labels outside [0, nd)");
   // both paths read whole 16-byte chunks of the operand rows, and the materialised path's
@@ -1010,16 +1150,27 @@ extern "C" int tt_infonce_bwd(int dtype, const void* qn, long bq, const void* dn
     const bf16_t* d = static_cast<const bf16_t*>(dn);
     float* slab = static_cast<float*>(ws);
     if (h == 256) {
-      TT_PROPAGATE((flash_role<256, true>(q, bq, d, nd, inv_tau, offdiag_sub, label_offset, lse, gscale, dqn, slab, st)));
-      TT_PROPAGATE((flash_role<256, false>(q, bq, d, nd, inv_tau, offdiag_sub, label_offset, lse, gscale, ddn, slab, st)));
+      TT_PROPAGATE((flash_role<256, true>(q, bq, d, nd, inv_tau, offdiag_sub, label_offset, lse, gscale, dqn, slab, st,
+                                            nullptr, rg, cg)));
+      TT_PROPAGATE((flash_role<256, false>(q, bq, d, nd, inv_tau, offdiag_sub, label_offset, lse, gscale, ddn, slab, st,
+                                            nullptr, rg, cg)));
     } else {
-      TT_PROPAGATE((flash_role<128, true>(q, bq, d, nd, inv_tau, offdiag_sub, label_offset, lse, gscale, dqn, slab, st)));
-      TT_PROPAGATE((flash_role<128, false>(q, bq, d, nd, inv_tau, offdiag_sub, label_offset, lse, gscale, ddn, slab, st)));
+      TT_PROPAGATE((flash_role<128, true>(q, bq, d, nd, inv_tau, offdiag_sub, label_offset, lse, gscale, dqn, slab, st,
+                                            nullptr, rg, cg)));
+      TT_PROPAGATE((flash_role<128, false>(q, bq, d, nd, inv_tau, offdiag_sub, label_offset, lse, gscale, ddn, slab, st,
+                                            nullptr, rg, cg)));
     }
     return 0;
   }
   return infonce_bwd_materialised<false>(dtype, qn, bq, dn, nd, h, inv_tau, offdiag_sub, label_offset, lse, nullptr,
-                                         gscale, dqn, ddn, ws, stream);
+                                         gscale, dqn, ddn, ws, stream, rg, cg);
+}
+
+extern "C" int tt_infonce_bwd(int dtype, const void* qn, long bq, const void* dn, long nd, int h, float inv_tau,
+                              float offdiag_sub, long label_offset, const float* lse, const float* gscale, float* dqn,
+                              float* ddn, void* ws, void* stream) {
+  return tt_infonce_bwd_grp(dtype, qn, bq, dn, nd, h, inv_tau, offdiag_sub, label_offset, nullptr, nullptr, lse,
+                            gscale, dqn, ddn, ws, stream);
 }
 
 // ------------------------------------------------------------ symmetric InfoNCE
@@ -1046,8 +1197,9 @@ extern "C" long tt_infonce_sym_fwd_ws_size(long n, int h) {
   return (2L * p.splits * n + n + 2L * p.rb * n) * (long)sizeof(float);
 }
 
-extern "C" int tt_infonce_sym_fwd(int dtype, const void* qn, const void* dn, long n, int h, float inv_tau,
-                                  float* lse_row, float* lse_col, float* row_loss, void* ws, void* stream) {
+extern "C" int tt_infonce_sym_fwd_grp(int dtype, const void* qn, const void* dn, long n, int h, float inv_tau,
+                                      const int32_t* group, float* lse_row, float* lse_col, float* row_loss,
+                                      void* ws, void* stream) {
   TT_CHECK_ARG(dtype == TT_DT_F32 || dtype == TT_DT_BF16, "tt_infonce_sym_fwd: bad dtype");
   TT_CHECK_ARG(h > 0 && (h * esize(dtype)) % 16 == 0, "tt_infonce_sym_fwd: h=%d misaligned", h);
   TT_CHECK_ARG(n >= 0 && n <= 65535L * 128, "tt_infonce_sym_fwd: n=%ld out of range", n);
@@ -1061,12 +1213,15 @@ extern "C" int tt_infonce_sym_fwd(int dtype, const void* qn, const void* dn, lon
   float* cpm = diag + n;
   float* cpl = cpm + (long)p.rb * n;
   dim3 grid(p.splits, p.rb);
-  if (dtype == TT_DT_BF16)
-    hipLaunchKernelGGL(infonce_sym_fwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)qn, (const bf16_t*)dn,
-                       n, h, inv_tau, p.per, pm, pl, cpm, cpl, diag);
-  else
-    hipLaunchKernelGGL(infonce_sym_fwd_kernel<float>, grid, dim3(256), 0, st, (const float*)qn, (const float*)dn, n,
-                       h, inv_tau, p.per, pm, pl, cpm, cpl, diag);
+#define TT_LAUNCH_SYM(T, G)                                                                                     \
+  hipLaunchKernelGGL((infonce_sym_fwd_kernel<T, G>), grid, dim3(256), 0, st, (const T*)qn, (const T*)dn, n, h, \
+                     inv_tau, p.per, pm, pl, cpm, cpl, diag, group)
+  if (dtype == TT_DT_BF16) {
+    if (group) TT_LAUNCH_SYM(bf16_t, true); else TT_LAUNCH_SYM(bf16_t, false);
+  } else {
+    if (group) TT_LAUNCH_SYM(float, true); else TT_LAUNCH_SYM(float, false);
+  }
+#undef TT_LAUNCH_SYM
   TT_CHECK_LAUNCH("infonce_sym_fwd_kernel");
   hipLaunchKernelGGL(infonce_sym_finalize_kernel, dim3(tt_ceil_div(n, 256)), dim3(256), 0, st, pm, pl, p.splits, cpm,
                      cpl, p.rb, n, diag, lse_row, lse_col, row_loss);
@@ -1074,14 +1229,19 @@ extern "C" int tt_infonce_sym_fwd(int dtype, const void* qn, const void* dn, lon
   return 0;
 }
 
+extern "C" int tt_infonce_sym_fwd(int dtype, const void* qn, const void* dn, long n, int h, float inv_tau,
+                                  float* lse_row, float* lse_col, float* row_loss, void* ws, void* stream) {
+  return tt_infonce_sym_fwd_grp(dtype, qn, dn, n, h, inv_tau, nullptr, lse_row, lse_col, row_loss, ws, stream);
+}
+
 extern "C" long tt_infonce_sym_bwd_ws_size(int dtype, long n, int h) {
   if (n <= 0) return 256;
   return tt_infonce_bwd_ws_size(dtype, n, n, h);
 }
 
-extern "C" int tt_infonce_sym_bwd(int dtype, const void* qn, const void* dn, long n, int h, float inv_tau,
-                                  const float* lse_row, const float* lse_col, const float* gscale, float* dqn,
-                                  float* ddn, void* ws, void* stream) {
+extern "C" int tt_infonce_sym_bwd_grp(int dtype, const void* qn, const void* dn, long n, int h, float inv_tau,
+                                      const int32_t* group, const float* lse_row, const float* lse_col,
+                                      const float* gscale, float* dqn, float* ddn, void* ws, void* stream) {
   TT_CHECK_ARG(dtype == TT_DT_F32 || dtype == TT_DT_BF16, "tt_infonce_sym_bwd: bad dtype");
   TT_CHECK_ARG(h > 0 && (h * esize(dtype)) % 16 == 0, "tt_infonce_sym_bwd: h=%d misaligned", h);
   TT_CHECK_ARG(n >= 0 && n <= 65535L * 128, "tt_infonce_sym_bwd: n=%ld out of range", n);
@@ -1094,16 +1254,26 @@ extern "C" int tt_infonce_sym_bwd(int dtype, const void* qn, const void* dn, lon
     const bf16_t* d = static_cast<const bf16_t*>(dn);
     float* slab = static_cast<float*>(ws);
     if (h == 256) {
-      TT_PROPAGATE((flash_role<256, true, true>(q, n, d, n, inv_tau, 0.f, 0, lse_row, gscale, dqn, slab, st, lse_col)));
-      TT_PROPAGATE((flash_role<256, false, true>(q, n, d, n, inv_tau, 0.f, 0, lse_row, gscale, ddn, slab, st, lse_col)));
+      TT_PROPAGATE((flash_role<256, true, true>(q, n, d, n, inv_tau, 0.f, 0, lse_row, gscale, dqn, slab, st, lse_col,
+                                                  group, group)));
+      TT_PROPAGATE((flash_role<256, false, true>(q, n, d, n, inv_tau, 0.f, 0, lse_row, gscale, ddn, slab, st, lse_col,
+                                                  group, group)));
     } else {
-      TT_PROPAGATE((flash_role<128, true, true>(q, n, d, n, inv_tau, 0.f, 0, lse_row, gscale, dqn, slab, st, lse_col)));
-      TT_PROPAGATE((flash_role<128, false, true>(q, n, d, n, inv_tau, 0.f, 0, lse_row, gscale, ddn, slab, st, lse_col)));
+      TT_PROPAGATE((flash_role<128, true, true>(q, n, d, n, inv_tau, 0.f, 0, lse_row, gscale, dqn, slab, st, lse_col,
+                                                  group, group)));
+      TT_PROPAGATE((flash_role<128, false, true>(q, n, d, n, inv_tau, 0.f, 0, lse_row, gscale, ddn, slab, st, lse_col,
+                                                  group, group)));
     }
     return 0;
   }
   return infonce_bwd_materialised<true>(dtype, qn, n, dn, n, h, inv_tau, 0.f, 0, lse_row, lse_col, gscale, dqn, ddn, ws,
-                                        stream);
+                                        stream, group, group);
+}
+
+extern "C" int tt_infonce_sym_bwd(int dtype, const void* qn, const void* dn, long n, int h, float inv_tau,
+                                  const float* lse_row, const float* lse_col, const float* gscale, float* dqn,
+                                  float* ddn, void* ws, void* stream) {
+  return tt_infonce_sym_bwd_grp(dtype, qn, dn, n, h, inv_tau, nullptr, lse_row, lse_col, gscale, dqn, ddn, ws, stream);
 }
 
 // ws: the score block S [bq, nd] fp32, then the per-chunk candidates (values, indices)
@@ -1164,6 +1334,75 @@ extern "C" int tt_hardneg_topk(int dtype, const void* qn, long bq, const void* d
   else
     hipLaunchKernelGGL((ttk::topk_merge_kernel<TOPK_MAX>), gm, dim3(256), 0, st, cv, ci, bq, ncand, k, idx, val);
   TT_CHECK_LAUNCH("topk_merge_kernel");
+  return 0;
+}
+
+// ------------------------------------------------- mining under the group rule
+// One wave per row walks the row's kin sorted candidates 64 at a time and keeps those the
+// group rule of tt_hip.h does not exclude, in order: a kept candidate's slot is the number
+// kept before it (earlier passes + the lanes below it in the ballot). No atomics.
+namespace {
+__global__ __launch_bounds__(256) void topk_drop_groups_kernel(const int32_t* __restrict__ idx_in,
+                                                               const float* __restrict__ val_in, long rows, int kin,
+                                                               long label_off, const int32_t* __restrict__ row_group,
+                                                               const int32_t* __restrict__ col_group, long nd, int k,
+                                                               int32_t* __restrict__ idx, float* __restrict__ val,
+                                                               int32_t* __restrict__ nkept) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const int g = row_group[row];
+  const long lab = label_off >= 0 ? label_off + row : -1;
+  int kept = 0;
+  // fill entry: the last one written, or the label column (-1) while nothing is
+  int last_i = lab >= 0 ? (int)lab : 0;
+  float last_v = -1.f;
+  for (int c0 = 0; c0 < kin && kept < k; c0 += 64) {
+    const int c = c0 + lane;
+    int col = -1;
+    float v = 0.f;
+    if (c < kin) {
+      col = idx_in[row * kin + c];
+      if (val_in) v = val_in[row * kin + c];
+    }
+    bool keep = col >= 0 && col < nd;
+    if (keep && col != lab && g >= 0 && col_group[col] == g) keep = false;
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(keep);
+    const int pos = kept + __builtin_popcountll(m & ((1ull << lane) - 1ull));
+    const bool wr = keep && pos < k;
+    if (wr) {
+      idx[row * k + pos] = col;
+      if (val) val[row * k + pos] = v;
+    }
+    const unsigned long long wm = __builtin_amdgcn_ballot_w64(wr);
+    if (wm) {
+      const int src = 63 - __builtin_clzll(wm);
+      last_i = __shfl(col, src, 64);
+      last_v = __shfl(v, src, 64);
+    }
+    kept += __builtin_popcountll(m);
+  }
+  const int nk = kept < k ? kept : k;
+  for (int s = nk + lane; s < k; s += 64) {
+    idx[row * k + s] = last_i;
+    if (val) val[row * k + s] = last_v;
+  }
+  if (nkept && lane == 0) nkept[row] = nk;
+}
+}  // namespace
+
+extern "C" int tt_topk_drop_groups(const int32_t* idx_in, const float* val_in, long rows, int kin, long label_offset,
+                                   const int32_t* row_group, const int32_t* col_group, long nd, int k, int32_t* idx,
+                                   float* val, int32_t* nkept, void* stream) {
+  TT_CHECK_ARG(k >= 1 && k <= kin, "tt_topk_drop_groups: k=%d needs 1 <= k <= kin=%d", k, kin);
+  TT_CHECK_ARG(rows >= 0 && nd >= 1 && nd < (1L << 31), "tt_topk_drop_groups: rows=%ld nd=%ld", rows, nd);
+  TT_CHECK_ARG(label_offset < 0 || label_offset + rows <= nd, "tt_topk_drop_groups: labels outside [0, nd)");
+  if (rows == 0) return 0;
+  TT_CHECK_ARG(idx_in && idx && row_group && col_group, "tt_topk_drop_groups: null idx_in, idx, row_group or col_group");
+  TT_CHECK_ARG(val == nullptr || val_in != nullptr, "tt_topk_drop_groups: val needs val_in");
+  hipLaunchKernelGGL(topk_drop_groups_kernel, dim3((unsigned)tt_ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream,
+                     idx_in, val_in, rows, kin, label_offset, row_group, col_group, nd, k, idx, val, nkept);
+  TT_CHECK_LAUNCH("topk_drop_groups_kernel");
   return 0;
 }
 

@@ -48,6 +48,8 @@ def parse(argv=None):
     ap.add_argument("--max_steps", type=int, default=0, help="stop after this many steps (0: full epochs)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log_every", type=int, default=20)
+    ap.add_argument("--mask_duplicates", action="store_true",
+                    help="mask in-batch false negatives by the store's group ids (pretok --groups)")
     return ap.parse_args(argv)
 
 
@@ -64,6 +66,9 @@ def main(argv=None):
         group = tdist.group.WORLD
     vocab = load_vocab(a.vocab)
     data = PairIds(a.ids, vocab)
+    if a.mask_duplicates and data.groups is None:
+        raise ValueError(f"--mask_duplicates: the pair store {a.ids} has no groups.npy; write it with "
+                         "`python -m two_towers_amd.pretok ... --groups`")
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
     torch.manual_seed(a.seed)  # identical initial weights on every rank
     E = vocab.vector_size
@@ -80,7 +85,9 @@ def main(argv=None):
     if a.loss == "infonce":
         crit = InfoNCELoss(temperature=tau, compute_dtype=dt, process_group=group)
     else:
-        crit = HardNegativeMarginLoss(k=5, margin=0.2, compute_dtype=dt, process_group=group)
+        # the store's largest group bounds every batch's and every gathered pool's: no sync per step
+        crit = HardNegativeMarginLoss(k=5, margin=0.2, compute_dtype=dt, process_group=group,
+                                      max_group_size=data.max_group_size if a.mask_duplicates else None)
     opt = Adam(model.parameters(), lr=lr)
     params = list(model.parameters())
 
@@ -99,11 +106,11 @@ def main(argv=None):
         total = torch.zeros((), device=dev)
         nb = 0
         t0 = time.perf_counter()
-        for i, (q, d) in enumerate(data.batches(a.batch_size, dev, shuffle=True, seed=a.seed + epoch, rank=rank,
-                                                world=world)):
+        for i, (q, d, *gids) in enumerate(data.batches(a.batch_size, dev, shuffle=True, seed=a.seed + epoch, rank=rank,
+                                                       world=world, with_groups=a.mask_duplicates)):
             opt.zero_grad(set_to_none=True)
             qv, dv = model(q, d)
-            loss = crit(qv, dv)
+            loss = crit(qv, dv, groups=gids[0]) if a.mask_duplicates else crit(qv, dv)
             loss.backward()
             tdp.allreduce_grads(params, group)
             opt.step()

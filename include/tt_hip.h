@@ -690,6 +690,22 @@ int tt_embed_grad_rows(const float* dx, long n, long ldx, const int32_t* perm, l
 long tt_embed_grad_ws_size(long m, int e);
 /* Sorted positions per workgroup of tt_embed_grad_rows (the chunk size C above). */
 int tt_embed_grad_chunk(void);
+/* tt_embed_grad_rows with the row of segment u placed at rows[dst[u]] of a larger buffer:
+ * the data-parallel form, where dst[u] is the position of this rank's u-th id in the union of
+ * all ranks' ids and the [nrows, e] buffers of the ranks are then summed by one all-reduce.
+ * dst int32 [nseg], strictly ascending; rows fp32 [nrows, e], nrows >= nseg. A dst[u] outside
+ * [0, nrows) drops that segment.
+ *  - every row of rows is written by the call, each element once: the rows no segment names
+ *    are +0.0f (also with nseg = 0, m = 0 or n = 0 while nrows > 0), so the caller clears
+ *    nothing; nrows = 0 is a no-op;
+ *  - the sums are the bits tt_embed_grad_rows gives for the same (dx, perm, seg_ptr): the
+ *    same chunks, the same order inside a chunk and across chunks; no float atomics;
+ *  - ws: tt_embed_grad_ws_size(m, e) bytes, as above;
+ *  - 16-byte accesses under the same rule as above (e % 4 == 0, ldx % 4 == 0, dx, rows, ws
+ *    16-byte aligned), else the scalar path. n, m, nrows < 2^31. */
+int tt_embed_grad_rows_at(const float* dx, long n, long ldx, const int32_t* perm, long m,
+                          const int32_t* seg_ptr, long nseg, const int32_t* dst, long nrows,
+                          int e, float* rows, void* ws, void* stream);
 
 /* torch.optim.SparseAdam's step (torch/optim/_functional.py sparse_adam) on the rows
  * ids[0..nrows) (distinct, int32) of weight / exp_avg / exp_avg_sq (fp32 [vocab, e]) with

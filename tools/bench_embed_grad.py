@@ -5,7 +5,8 @@ E 300, H 512, bf16), each piece alone, HIP-event timed on the launching stream:
   sparse_adam_rows   the lazy Adam step on the touched rows (tt_sparse_adam_rows)
 for ids drawn uniformly and Zipf(1.0) over 20 000 and 3 000 000 rows with 10 % pads. Bytes are
 algorithmic (rows read once, outputs written once, indices); the fraction is of the 8.0 TB/s
-HBM spec. One JSON line per measurement; no threshold."""
+HBM spec. One JSON line per measurement; no threshold.
+--union 2,4,8 times the data-parallel form instead (tt_embed_grad_rows_at, see union())."""
 import argparse
 import json
 import os
@@ -98,6 +99,44 @@ def embed(dX, vocab, dist, pad, E, iters, with_adam):
     return out
 
 
+def union(dX, vocab, pad, E, iters, ratios, reps):
+    """The data-parallel form on one (dx, perm, seg_ptr) with Zipf ids: tt_embed_grad_rows, then
+    tt_embed_grad_rows_at with the identity dst (nrows = U) and with nrows = R U, dst spread
+    evenly (every R-th row named), which adds (R - 1) U E 4 bytes of zero stores. The variants
+    are timed in turn, `reps` rounds of `iters` calls; ms is the median round, ms_min / ms_max
+    the spread between rounds. Bytes are algorithmic, as above, plus the dst entries."""
+    n = dX.shape[0]
+    g = torch.Generator(device="cuda").manual_seed(vocab % 1000 + 4)
+    ids = draw_ids(n, vocab, "zipf", pad, g)
+    perm, seg_ptr, uniq = ops.embed_plan(ids)
+    m, U = perm.numel(), uniq.numel()
+    ws = torch.empty(_lib.load().tt_embed_grad_ws_size(m, E), dtype=torch.uint8, device="cuda")
+    base = torch.empty(U, E, dtype=torch.float32, device="cuda")
+    variants = [("embed_grad_rows", 0, lambda: ops.embed_grad_rows(dX, perm, seg_ptr, E, rows=base, ws=ws))]
+    variants[0][2]()
+    for r in [1] + list(ratios):
+        dst = (torch.arange(U, device="cuda", dtype=torch.int64) * r).to(torch.int32)
+        rows = torch.empty(r * U, E, dtype=torch.float32, device="cuda")
+        variants.append(("embed_grad_rows_at", r, lambda dst=dst, rows=rows, r=r: ops.embed_grad_rows_at(
+            dX, perm, seg_ptr, dst, r * U, E, rows=rows, ws=ws)))
+        variants[-1][2]()
+        assert torch.equal(rows[::r], base), "not the plain kernel's bits"
+        assert r == 1 or not bool(rows.view(U, r, E)[:, 1:].any()), "an unnamed row is not zero"
+    times = [[] for _ in variants]
+    for _ in range(reps):
+        for i, (_, _, f) in enumerate(variants):
+            times[i].append(timed(f, iters))
+    out = []
+    for (op, r, _), t in zip(variants, times):
+        t = sorted(t)
+        ms = t[len(t) // 2]
+        nbytes = 4.0 * (m * E + max(r, 1) * U * E) + 4.0 * (m + U + 1 + (U if r else 0))
+        out.append({"op": op, "nrows_over_U": r, "vocab": vocab, "ids": "zipf", "n": n, "m": m, "U": U,
+                    "ms": round(ms, 4), "ms_min": round(t[0], 4), "ms_max": round(t[-1], 4),
+                    "gbs": round(nbytes / ms / 1e6, 1), "hbm_frac": round(nbytes / ms / 1e6 / HBM_PEAK_GBS, 4)})
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
@@ -109,11 +148,19 @@ if __name__ == "__main__":
     ap.add_argument("--vocabs", default="20000,3000000")
     ap.add_argument("--pad", type=float, default=0.1)
     ap.add_argument("--no-adam", action="store_true")
+    ap.add_argument("--union", default="", metavar="R[,R...]",
+                    help="time tt_embed_grad_rows_at instead: identity dst, then nrows = R U for each R (2,4,8)")
+    ap.add_argument("--reps", type=int, default=7, help="--union: rounds over the variants (spread)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_embed_grad.py needs the GPU")
     rec, dX = dgrad_l0(a.towers, a.batch * a.seq, a.emb, 2 * a.hidden, a.iters)
     print(json.dumps(rec), flush=True)
+    if a.union:
+        for vocab in (int(v) for v in a.vocabs.split(",")):
+            for r in union(dX, vocab, a.pad, a.emb, a.iters, [int(x) for x in a.union.split(",")], a.reps):
+                print(json.dumps(r), flush=True)
+        sys.exit(0)
     for vocab in (int(v) for v in a.vocabs.split(",")):
         for dist in ("uniform", "zipf"):
             for r in embed(dX, vocab, dist, a.pad, a.emb, a.iters, not a.no_adam):

@@ -229,6 +229,8 @@ _SIGS = {
                                     c_void_p]),
     "tt_embed_grad_rows": (c_int, [c_void_p, c_long, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_void_p,
                                    c_void_p, c_void_p]),
+    "tt_embed_grad_rows_at": (c_int, [c_void_p, c_long, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p, c_long,
+                                      c_int, c_void_p, c_void_p, c_void_p]),
     "tt_embed_grad_ws_size": (c_long, [c_long, c_int]),
     "tt_embed_grad_chunk": (c_int, []),
     "tt_sparse_adam_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p, c_void_p, c_long, c_int,

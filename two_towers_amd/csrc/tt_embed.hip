@@ -1,6 +1,7 @@
 // Trainable embedding table: the per-token gradient rows of the layer-0 data gradient summed
-// by token id (tt_embed_grad_rows), and torch.optim.SparseAdam's update of the touched rows
-// with the compute-dtype copy kept in step (tt_sparse_adam_rows). Both are HBM-bound.
+// by token id (tt_embed_grad_rows; tt_embed_grad_rows_at puts them at given rows of an otherwise
+// zero buffer, which data-parallel ranks then sum), and torch.optim.SparseAdam's update of the
+// touched rows with the compute-dtype copy kept in step (tt_sparse_adam_rows). All are HBM-bound.
 #include <math.h>
 
 #include <algorithm>
@@ -46,11 +47,13 @@ TT_DEV int segment_of(const int32_t* __restrict__ seg_ptr, int U, long p) {
 // rows[u]; the part of a segment that crosses the chunk's start goes to ws slot 2k, the part
 // of one that starts inside and crosses its end to slot 2k+1 (a segment covering the whole
 // chunk crosses the start: slot 2k).
-template <int VEC>
-__global__ __launch_bounds__(256) void embed_grad_chunk_kernel(const float* __restrict__ dx, long n, long ldx,
-                                                               const int32_t* __restrict__ perm, long m,
-                                                               const int32_t* __restrict__ seg_ptr, int U, int E,
-                                                               float* __restrict__ rows, float* __restrict__ ws) {
+// AT: segment u's row is rows[dst[u]] of an [nrows, E] buffer instead of rows[u]; a dst[u]
+// outside [0, nrows) drops the segment (tt_embed_grad_rows_at). The sums are the same code.
+template <int VEC, bool AT>
+TT_DEV void embed_grad_chunk_body(const float* __restrict__ dx, long n, long ldx, const int32_t* __restrict__ perm,
+                                  long m, const int32_t* __restrict__ seg_ptr, int U, int E,
+                                  const int32_t* __restrict__ dst, int nrows, float* __restrict__ rows,
+                                  float* __restrict__ ws) {
   typedef typename Vec<VEC>::T V;
   const long k = blockIdx.x;
   const long p0 = k * CHUNK;
@@ -85,8 +88,17 @@ __global__ __launch_bounds__(256) void embed_grad_chunk_kernel(const float* __re
         Vec<VEC>::add(acc, Vec<VEC>::sel(ok, v));
       }
       if (seg_end <= p1) {  // the segment ends in this chunk
-        float* dst = head ? ws + (2 * k) * (long)E : rows + (long)u * E;
-        *reinterpret_cast<V*>(dst + (long)c * VEC) = acc;
+        if constexpr (AT) {
+          if (head) {
+            *reinterpret_cast<V*>(ws + (2 * k) * (long)E + (long)c * VEC) = acc;
+          } else {
+            const int r = dst[u];
+            if ((unsigned)r < (unsigned)nrows) *reinterpret_cast<V*>(rows + (long)r * E + (long)c * VEC) = acc;
+          }
+        } else {
+          float* out = head ? ws + (2 * k) * (long)E : rows + (long)u * E;
+          *reinterpret_cast<V*>(out + (long)c * VEC) = acc;
+        }
         head = false;
         acc = Vec<VEC>::zero();
         ++u;
@@ -99,14 +111,68 @@ __global__ __launch_bounds__(256) void embed_grad_chunk_kernel(const float* __re
   }
 }
 
+template <int VEC>
+__global__ __launch_bounds__(256) void embed_grad_chunk_kernel(const float* __restrict__ dx, long n, long ldx,
+                                                               const int32_t* __restrict__ perm, long m,
+                                                               const int32_t* __restrict__ seg_ptr, int U, int E,
+                                                               float* __restrict__ rows, float* __restrict__ ws) {
+  embed_grad_chunk_body<VEC, false>(dx, n, ldx, perm, m, seg_ptr, U, E, nullptr, 0, rows, ws);
+}
+
+// Rows of the [nrows, E] buffer per workgroup of tt_embed_grad_rows_at's zero pass.
+constexpr int ZROWS = 64;
+
+// Workgroup z owns rows [z ZROWS, (z+1) ZROWS) and stores +0 to those no dst entry names: one
+// lower bound in dst (ascending), then a walk along it; a run of unnamed rows is one contiguous
+// range, stored by all threads. The named rows are left to the workgroups that sum them, so no
+// element is written twice. Whatever dst holds, the stores stay inside the workgroup's rows.
+template <int VEC>
+TT_DEV void zero_unnamed_rows(const int32_t* __restrict__ dst, int U, int nrows, int E, float* __restrict__ rows,
+                              long z) {
+  typedef typename Vec<VEC>::T V;
+  const long r0 = z * ZROWS;
+  const long r1 = std::min<long>(nrows, r0 + ZROWS);
+  int j = 0, hi = U;  // first j with dst[j] >= r0
+  while (j < hi) {
+    const int mid = j + ((hi - j) >> 1);
+    if ((long)dst[mid] < r0) j = mid + 1; else hi = mid;
+  }
+  for (long r = r0; r < r1; ++j) {
+    long named = r1;  // the next named row, or the end
+    if (j < U) {
+      const long d = dst[j];
+      named = d < r ? r : (d < r1 ? d : r1);
+    }
+    const long b = named * E / VEC;
+    for (long i = r * E / VEC + threadIdx.x; i < b; i += blockDim.x) reinterpret_cast<V*>(rows)[i] = Vec<VEC>::zero();
+    r = named + 1;
+  }
+}
+
+// tt_embed_grad_rows_at's first launch: workgroups [0, nchunks) are embed_grad_chunk_kernel's with
+// the row of segment u at dst[u], the ones after them run the zero pass beside the gathers.
+template <int VEC>
+__global__ __launch_bounds__(256) void embed_grad_chunk_at_kernel(const float* __restrict__ dx, long n, long ldx,
+                                                                  const int32_t* __restrict__ perm, long m,
+                                                                  const int32_t* __restrict__ seg_ptr, int U, int E,
+                                                                  const int32_t* __restrict__ dst, int nrows,
+                                                                  long nchunks, float* __restrict__ rows,
+                                                                  float* __restrict__ ws) {
+  if ((long)blockIdx.x >= nchunks) {
+    zero_unnamed_rows<VEC>(dst, U, nrows, E, rows, (long)blockIdx.x - nchunks);
+    return;
+  }
+  embed_grad_chunk_body<VEC, true>(dx, n, ldx, perm, m, seg_ptr, U, E, dst, nrows, rows, ws);
+}
+
 // Workgroup b - 1 looks at chunk boundary b (position b CHUNK). The segment u holding that
 // position crosses it if it starts before it; the workgroup of the first boundary a segment
 // crosses adds the segment's partials in chunk order: slot 2 k0 + 1 of the chunk it starts
-// in, then slot 2k of every later chunk it reaches.
-template <int VEC>
-__global__ __launch_bounds__(256) void embed_grad_cross_kernel(long m, const int32_t* __restrict__ seg_ptr, int U,
-                                                               int E, float* __restrict__ rows,
-                                                               const float* __restrict__ ws) {
+// in, then slot 2k of every later chunk it reaches. AT as embed_grad_chunk_body.
+template <int VEC, bool AT>
+TT_DEV void embed_grad_cross_body(long m, const int32_t* __restrict__ seg_ptr, int U, int E,
+                                  const int32_t* __restrict__ dst, int nrows, float* __restrict__ rows,
+                                  const float* __restrict__ ws) {
   typedef typename Vec<VEC>::T V;
   const long b = (long)blockIdx.x + 1;
   const long p = b * CHUNK;
@@ -127,8 +193,28 @@ __global__ __launch_bounds__(256) void embed_grad_cross_kernel(long m, const int
       for (int i = 0; i < UNROLL; ++i) Vec<VEC>::add(acc, v[i]);
     }
     for (; k <= k1; ++k) Vec<VEC>::add(acc, *reinterpret_cast<const V*>(ws + (2 * k) * (long)E + (long)c * VEC));
-    *reinterpret_cast<V*>(rows + (long)u * E + (long)c * VEC) = acc;
+    if constexpr (AT) {
+      const int r = dst[u];
+      if ((unsigned)r < (unsigned)nrows) *reinterpret_cast<V*>(rows + (long)r * E + (long)c * VEC) = acc;
+    } else {
+      *reinterpret_cast<V*>(rows + (long)u * E + (long)c * VEC) = acc;
+    }
   }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void embed_grad_cross_kernel(long m, const int32_t* __restrict__ seg_ptr, int U,
+                                                               int E, float* __restrict__ rows,
+                                                               const float* __restrict__ ws) {
+  embed_grad_cross_body<VEC, false>(m, seg_ptr, U, E, nullptr, 0, rows, ws);
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void embed_grad_cross_at_kernel(long m, const int32_t* __restrict__ seg_ptr, int U,
+                                                                  int E, const int32_t* __restrict__ dst, int nrows,
+                                                                  float* __restrict__ rows,
+                                                                  const float* __restrict__ ws) {
+  embed_grad_cross_body<VEC, true>(m, seg_ptr, U, E, dst, nrows, rows, ws);
 }
 
 inline int block_for(int ncol) { return std::min(256, std::max(64, (ncol + 63) / 64 * 64)); }
@@ -257,6 +343,56 @@ extern "C" int tt_embed_grad_rows(const float* dx, long n, long ldx, const int32
       hipLaunchKernelGGL(embed_grad_cross_kernel<1>, dim3((unsigned)(nchunks - 1)), dim3(bs), 0, st, m, seg_ptr, nu, e,
                          rows, w);
       TT_CHECK_LAUNCH("embed_grad_cross_kernel");
+    }
+  }
+  return 0;
+}
+
+extern "C" int tt_embed_grad_rows_at(const float* dx, long n, long ldx, const int32_t* perm, long m,
+                                     const int32_t* seg_ptr, long nseg, const int32_t* dst, long nrows, int e,
+                                     float* rows, void* ws, void* stream) {
+  TT_CHECK_ARG(n >= 0 && m >= 0 && nseg >= 0 && nrows >= 0 && e >= 1,
+               "tt_embed_grad_rows_at: bad sizes (n %ld m %ld U %ld rows %ld E %d)", n, m, nseg, nrows, e);
+  TT_CHECK_ARG(n < (1L << 31) && m < (1L << 31) && nseg < (1L << 31) && nrows < (1L << 31),
+               "tt_embed_grad_rows_at: row numbers and positions are int32");
+  TT_CHECK_ARG(nseg <= m, "tt_embed_grad_rows_at: %ld segments over %ld positions", nseg, m);
+  TT_CHECK_ARG(nseg <= nrows, "tt_embed_grad_rows_at: %ld segments for %ld rows", nseg, nrows);
+  if (nrows == 0) return 0;
+  TT_CHECK_ARG(rows, "tt_embed_grad_rows_at: null operand");
+  // nothing to sum (an out-of-range perm entry adds nothing, so n = 0 sums to +0 as well):
+  // the zero pass alone writes every row
+  const bool sums = nseg > 0 && m > 0 && n > 0;
+  if (sums) {
+    TT_CHECK_ARG(ldx >= e, "tt_embed_grad_rows_at: ldx %ld < E %d", ldx, e);
+    TT_CHECK_ARG(dx && perm && seg_ptr && dst && ws, "tt_embed_grad_rows_at: null operand");
+  }
+  const long nchunks = sums ? tt_ceil_div(m, CHUNK) : 0;
+  const long nzero = tt_ceil_div(nrows, ZROWS);
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = e % 4 == 0 && (!sums || (ldx % 4 == 0 && ((uintptr_t)dx | (uintptr_t)ws) % 16 == 0)) &&
+                   (uintptr_t)rows % 16 == 0;
+  const int nu = sums ? (int)nseg : 0;
+  const int nr = (int)nrows;
+  float* w = static_cast<float*>(ws);
+  if (vec) {
+    const int bs = block_for(e / 4);
+    hipLaunchKernelGGL(embed_grad_chunk_at_kernel<4>, dim3((unsigned)(nchunks + nzero)), dim3(bs), 0, st, dx, n, ldx,
+                       perm, m, seg_ptr, nu, e, dst, nr, nchunks, rows, w);
+    TT_CHECK_LAUNCH("embed_grad_chunk_at_kernel");
+    if (nchunks > 1) {
+      hipLaunchKernelGGL(embed_grad_cross_at_kernel<4>, dim3((unsigned)(nchunks - 1)), dim3(bs), 0, st, m, seg_ptr, nu,
+                         e, dst, nr, rows, w);
+      TT_CHECK_LAUNCH("embed_grad_cross_at_kernel");
+    }
+  } else {
+    const int bs = block_for(e);
+    hipLaunchKernelGGL(embed_grad_chunk_at_kernel<1>, dim3((unsigned)(nchunks + nzero)), dim3(bs), 0, st, dx, n, ldx,
+                       perm, m, seg_ptr, nu, e, dst, nr, nchunks, rows, w);
+    TT_CHECK_LAUNCH("embed_grad_chunk_at_kernel");
+    if (nchunks > 1) {
+      hipLaunchKernelGGL(embed_grad_cross_at_kernel<1>, dim3((unsigned)(nchunks - 1)), dim3(bs), 0, st, m, seg_ptr, nu,
+                         e, dst, nr, rows, w);
+      TT_CHECK_LAUNCH("embed_grad_cross_at_kernel");
     }
   }
   return 0;

@@ -61,6 +61,37 @@ def all_reduce_sum_(t: torch.Tensor, group=None):
     return t
 
 
+def union_of(id_lists):
+    """The ascending union of ascending, distinct int64 id lists and, per list, the int32
+    positions of its ids inside the union: (guniq [G], [dst_r [U_r]]), guniq[dst_r] == ids_r.
+    Pure torch, no collectives: every rank that holds the same lists computes the same result."""
+    if not id_lists:
+        raise ValueError("union_of needs at least one id list")
+    lists = [t.reshape(-1).to(torch.int64) for t in id_lists]
+    guniq = torch.unique(torch.cat(lists))  # sorted
+    return guniq, [torch.searchsorted(guniq, t).to(torch.int32) for t in lists]
+
+
+def union_ids(local_ids: torch.Tensor, group=None):
+    """The collective form of union_of for this rank's distinct ids (ascending int64 [U], may be
+    empty): (guniq [G], dst int32 [U]) with guniq the same on every rank. Two all-gathers: the
+    counts (read on the host, to size the second), then the ids padded with -1 to the largest
+    count. Without an active group the union is the list itself."""
+    ids = local_ids.reshape(-1).to(torch.int64)
+    if not active(group):
+        return ids, torch.arange(ids.numel(), dtype=torch.int32, device=ids.device)
+    r, w = rank_world(group)
+    counts = all_gather_rows(torch.tensor([ids.numel()], dtype=torch.int64, device=ids.device), group).tolist()
+    width = max(counts)
+    if width == 0:
+        return ids, torch.zeros(0, dtype=torch.int32, device=ids.device)
+    padded = torch.full((width,), -1, dtype=torch.int64, device=ids.device)
+    padded[:ids.numel()] = ids
+    every = all_gather_rows(padded, group).view(w, width)
+    guniq, dst = union_of([every[i, :c] for i, c in enumerate(counts)])
+    return guniq, dst[r]
+
+
 class GatherRows(torch.autograd.Function):
     """Differentiable all-gather: backward reduce-scatters the gradient."""
 

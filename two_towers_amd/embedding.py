@@ -18,6 +18,10 @@ catches a replaced table (EmbeddingTable._sample).
 After a backward, weight.grad is a coalesced torch.sparse_coo_tensor [V, E] whose indices
 are the distinct ids of the batch: nn.Embedding(sparse=True)'s contract.
 
+Under data parallelism the table opts in with table.set_process_group(group): the indices are
+then the distinct ids of the global batch and the values the sums over all ranks, the same bits
+on every rank (towers.py, dist.union_ids).
+
 The module is never registered as a submodule of a model (the reference's state_dict keys
 stay); it has its own state_dict.
 """
@@ -29,7 +33,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import _lib, dist, ops
 
 _tables: "weakref.WeakSet[EmbeddingTable]" = weakref.WeakSet()
 _NSAMPLE = 4096
@@ -51,6 +55,7 @@ class EmbeddingTable(nn.Module):
             raise ValueError("EmbeddingTable rows are addressed by int32 token ids")
         self.weight = nn.Parameter(w.detach().to(torch.float32).clone().contiguous(), requires_grad=bool(trainable))
         self._copy = None  # (key, [V, Ep] compute-dtype copy, sample of weight)
+        self.dp_group = None  # (group,) once set_process_group has opted in to data parallelism
         _tables.add(self)
 
     @property
@@ -64,6 +69,20 @@ class EmbeddingTable(nn.Module):
     @property
     def embedding_dim(self) -> int:
         return self.weight.shape[1]
+
+    def set_process_group(self, group=None):
+        """Train this table under data parallelism over `group` (None: the default group). Each
+        backward then leaves the same coalesced sparse gradient on every rank: the rows of the
+        ids any rank saw, summed across ranks (towers.py, dist.union_ids), so the same
+        SparseAdam step everywhere keeps the tables and their moments bit-identical. Rank 0's
+        weight is broadcast once, here. Without an active group the table trains as on one rank."""
+        self.dp_group = (group,)
+        if dist.active(group):
+            src = 0 if group is None else torch.distributed.get_global_rank(group, 0)
+            with torch.no_grad():
+                torch.distributed.broadcast(self.weight, src, group=group)
+            torch.autograd.graph.increment_version(self.weight)  # written in place: the compute copy rebuilds
+        return self
 
     def _key(self, dt, ep):
         w = self.weight

@@ -125,6 +125,29 @@ def embed_grad_rows(dx: torch.Tensor, perm: torch.Tensor, seg_ptr: torch.Tensor,
     return rows
 
 
+def embed_grad_rows_at(dx: torch.Tensor, perm: torch.Tensor, seg_ptr: torch.Tensor, dst: torch.Tensor, nrows: int,
+                       e: int | None = None, rows: torch.Tensor | None = None,
+                       ws: torch.Tensor | None = None) -> torch.Tensor:
+    """embed_grad_rows with segment u's sum at rows[dst[u]] of an fp32 [nrows, e] buffer whose
+    other rows the call zeroes (tt_embed_grad_rows_at): dst int32 [U], strictly ascending."""
+    assert dx.dtype == torch.float32 and dx.dim() == 2 and dx.stride(1) == 1
+    assert perm.dtype == torch.int32 and perm.is_contiguous() and seg_ptr.dtype == torch.int32 and seg_ptr.is_contiguous()
+    assert dst.dtype == torch.int32 and dst.is_contiguous()
+    _lib.require_gpu(dx, perm, seg_ptr, dst)
+    e = dx.shape[1] if e is None else e
+    u, m = seg_ptr.numel() - 1, perm.numel()
+    assert dst.numel() == u and nrows >= u
+    if rows is None:
+        rows = torch.empty(nrows, e, dtype=torch.float32, device=dx.device)
+    assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.numel() >= nrows * e
+    if ws is None:
+        ws = torch.empty(_lib.load().tt_embed_grad_ws_size(m, e), dtype=torch.uint8, device=dx.device)
+    assert ws.numel() * ws.element_size() >= _lib.load().tt_embed_grad_ws_size(m, e)
+    call("tt_embed_grad_rows_at", dx.data_ptr(), dx.shape[0], dx.stride(0), perm.data_ptr(), m, seg_ptr.data_ptr(), u,
+         dst.data_ptr(), nrows, e, rows.data_ptr(), ws.data_ptr(), stream_ptr(dx.device))
+    return rows
+
+
 def sparse_adam_rows(weight: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, ids: torch.Tensor,
                      rows: torch.Tensor, copy: torch.Tensor | None, *, lr: float, beta1: float, beta2: float,
                      eps: float, step: int, guard: torch.Tensor | None = None):

@@ -607,7 +607,7 @@ class TowersFn(torch.autograd.Function):
     gradient. Float inputs that require grad receive dL/dx as [B, T, E] fp32."""
 
     @staticmethod
-    def forward(ctx, cfg: TowerCfg, table, group, cache_ok, *args):
+    def forward(ctx, cfg: TowerCfg, table, group, emb_group, cache_ok, *args):
         n = cfg.ntowers
         emb_w = args[-1] if len(args) == n + n * cfg.nparams + 1 else None
         xs, params = args[:n], args[n:n + n * cfg.nparams]
@@ -653,14 +653,19 @@ class TowersFn(torch.autograd.Function):
         # table, the index plumbing of its sparse gradient (which positions share a token id)
         # depends on the ids alone and is built here, so that nothing but the segment-sum
         # kernels sits between the data-gradient GEMM and the optimiser in the backward
-        ctx.x_grad = tuple(bool(ctx.needs_input_grad[4 + i]) and xs[i].is_floating_point() for i in range(n))
+        ctx.x_grad = tuple(bool(ctx.needs_input_grad[5 + i]) and xs[i].is_floating_point() for i in range(n))
         ctx.emb = None
         if emb_w is not None and ctx.needs_input_grad[-1] and not xs[0].is_floating_point():
             if tuple(emb_w.shape) != (table.shape[0], E) or emb_w.dtype != torch.float32:
                 raise _lib.TTError(f"embedding weight must be fp32 [{table.shape[0]}, {E}], got {emb_w.dtype} "
                                    f"{tuple(emb_w.shape)}")
             ids = torch.cat([x.reshape(-1) for x in xs])  # one row space: a token of both towers is one row
-            ctx.emb = (*ops.embed_plan(ids.masked_fill(ids >= table.shape[0], -1)), emb_w)
+            perm, seg_ptr, uniq = ops.embed_plan(ids.masked_fill(ids >= table.shape[0], -1))
+            # data-parallel table (emb_group): the ranks agree here on the ascending union of
+            # their distinct ids and each keeps the positions of its own ids inside it, so the
+            # backward adds nothing data-dependent before its one all-reduce of the rows
+            guniq, dst = dist.union_ids(uniq, emb_group[0]) if emb_group is not None else (None, None)
+            ctx.emb = (perm, seg_ptr, uniq, emb_w, guniq, dst, emb_group)
             if not getattr(emb_w, "_tt_grad_hook", False):
                 emb_w.register_post_accumulate_grad_hook(embedding.keep_coalesced)
                 emb_w._tt_grad_hook = True
@@ -783,10 +788,13 @@ class TowersFn(torch.autograd.Function):
         # ---- GRU layer 0
         dG0, dbih0, dbhh0 = _gru_layer_bwd(cfg, 0, B, T, S0, Y0, dY0, None, packs, yprev=yp0)
         del dY0
-        dxs, demb = _input_grads(ctx, cfg, B, T, Ep, dG0, packs)
+        dxs, demb, emb_work = _input_grads(ctx, cfg, B, T, Ep, dG0, packs)
+        # a data-parallel table's rows are summed across ranks (emb_work) under these two GEMMs
         dWih0, dWhh0 = _weight_grads(cfg, B, T, dG0, X0, Ep, Ep, Y0, kr=E, yprev=yp0)
         gl0 = [{} for _ in range(n)]
         _layer_grads(gl0, 0, E, Ep, dWih0, dWhh0, dbih0, dbhh0)
+        if emb_work is not None:
+            emb_work.wait()
         if side is not None:
             main.wait_stream(side)
             for t in [*[v for d in gl for v in d.values()], *[g for hg in head_grads for g in hg]]:
@@ -803,8 +811,8 @@ class TowersFn(torch.autograd.Function):
         ctx.packs = None
         ctx.params = None
         ctx.emb = None
-        tail = (demb,) if len(ctx.needs_input_grad) == 4 + n + len(grads) + 1 else ()
-        return (None, None, None, None, *dxs, *grads, *tail)
+        tail = (demb,) if len(ctx.needs_input_grad) == 5 + n + len(grads) + 1 else ()
+        return (None, None, None, None, None, *dxs, *grads, *tail)
 
 
 def _input_grads(ctx, cfg, B, T, Ep, dG0, packs):
@@ -816,7 +824,7 @@ def _input_grads(ctx, cfg, B, T, Ep, dG0, packs):
     n, dt, E, H = cfg.ntowers, cfg.dtype, cfg.E, cfg.H
     want_x, emb = any(ctx.x_grad), ctx.emb
     if not want_x and emb is None:
-        return [None] * n, None
+        return [None] * n, None, None
     dev = dG0[0].device
     BT = B * T
     dX = _alloc((n * BT, E), torch.float32, dev)
@@ -827,14 +835,29 @@ def _input_grads(ctx, cfg, B, T, Ep, dG0, packs):
                  a_kouter=False, b_kouter=True, dtype=dt, out_dtype=torch.float32)
     dxs = [parts[ti].view(B, T, E) if ctx.x_grad[ti] else None for ti in range(n)]
     if emb is None:
-        return dxs, None
-    perm, seg_ptr, uniq, emb_w = emb
+        return dxs, None, None
+    perm, seg_ptr, uniq, emb_w, guniq, dst, emb_group = emb
     m, U, V = perm.numel(), uniq.numel(), emb_w.shape[0]
-    emb_w._tt_grad_ids = uniq  # embedding.keep_coalesced: autograd's stored copy drops the coalesced flag
-    with timing.region("embed_grad_rows", 2, 4.0 * (m + U) * E, float(4 * (m + U) * E + 4 * (m + U + 1)),
-                       kernel="embed_grad_chunk_kernel"):
-        rows = ops.embed_grad_rows(dX, perm, seg_ptr)
-    return dxs, torch.sparse_coo_tensor(uniq.unsqueeze(0), rows, (V, E), is_coalesced=True)
+    if emb_group is None:
+        emb_w._tt_grad_ids = uniq  # embedding.keep_coalesced: autograd's stored copy drops the coalesced flag
+        with timing.region("embed_grad_rows", 2, 4.0 * (m + U) * E, float(4 * (m + U) * E + 4 * (m + U + 1)),
+                           kernel="embed_grad_chunk_kernel"):
+            rows = ops.embed_grad_rows(dX, perm, seg_ptr)
+        return dxs, torch.sparse_coo_tensor(uniq.unsqueeze(0), rows, (V, E), is_coalesced=True), None
+    # data parallel: this rank's sums at their positions in the union of all ranks' ids, zero
+    # rows for the ids it did not see, then one flat fp32 all-reduce of [G, E]. Every rank ends
+    # with the same bits. The collective is asynchronous (RCCL: on its own stream, ordered
+    # after the kernel above); TowersFn.backward waits for it after the layer-0 weight gradients.
+    G = guniq.numel()
+    emb_w._tt_grad_ids = guniq
+    emb_w._tt_dp_reduced = True  # dist.allreduce_grads: already summed (and not a flat tensor)
+    with timing.region("embed_grad_rows", 2, 4.0 * (m + U) * E, float(4 * (m + G) * E + 4 * (m + 2 * U + 1)),
+                       kernel="embed_grad_chunk_at_kernel"):
+        rows = ops.embed_grad_rows_at(dX, perm, seg_ptr, dst, G)
+    work = None
+    if G > 0:  # the same G on every rank: all of them skip the collective, or none
+        work = torch.distributed.all_reduce(rows, op=torch.distributed.ReduceOp.SUM, group=emb_group[0], async_op=True)
+    return dxs, torch.sparse_coo_tensor(guniq.unsqueeze(0), rows, (V, E), is_coalesced=True), work
 
 
 def _layer_grads(gl, layer, E, Ep, dWih, dWhh, dbih, dbhh):
@@ -865,16 +888,24 @@ def run_towers(cfg: TowerCfg, table, xs, params, reduce_group=None, reduce: bool
     """reduce: sum the gradients across the data-parallel reduce_group's ranks during the
     backward (dist.OverlapReducer); ignored unless that group spans more than one rank.
     emb: the trainable EmbeddingTable whose compute copy `table` is (token-id inputs), or
-    None; its weight then receives a sparse gradient."""
+    None; its weight then receives a sparse gradient. Under an active process group the table
+    must have opted in (EmbeddingTable.set_process_group): the gradient is then the global
+    batch's on every rank, over the union of the ranks' ids."""
     if cfg.H % 8:
         raise ValueError(f"GRU hidden size {cfg.H} must be a multiple of 8 on the HIP path "
                          "(the step epilogues update 8 consecutive units per thread)")
     group = (reduce_group,) if reduce and dist.active(reduce_group) else None
     grad_on = torch.is_grad_enabled()
     emb_w = emb.weight if emb is not None and grad_on and emb.weight.requires_grad else None
-    if emb_w is not None and dist.rank_world(reduce_group)[1] > 1:
-        raise _lib.TTError("a trainable EmbeddingTable is not supported under data parallelism yet (the ranks' "
-                           "sparse row gradients are not gathered): freeze it (trainable=False) or train on one rank")
+    emb_group = None
+    if emb_w is not None:
+        opted = getattr(emb, "dp_group", None)  # (group,) after EmbeddingTable.set_process_group
+        if opted is None and dist.rank_world(reduce_group)[1] > 1:
+            raise _lib.TTError("a trainable EmbeddingTable under data parallelism has to opt in (the ranks' sparse "
+                               "row gradients are summed only then): call table.set_process_group(group), freeze "
+                               "the table (trainable=False) or train on one rank")
+        if opted is not None and dist.active(opted[0]):
+            emb_group = opted
     # inference (no gradient wanted): the packed compute copies may be reused while the
     # parameters are unchanged (retrieval / serving encode many batches per weight version)
     cache_ok = not (grad_on and any(p.requires_grad for p in params))
@@ -885,5 +916,5 @@ def run_towers(cfg: TowerCfg, table, xs, params, reduce_group=None, reduce: bool
         # no-grad call of a model in train() mode still draws dropout, so it stays below)
         return towers_infer(cfg, table, xs, params)
     if emb_w is not None:
-        return TowersFn.apply(cfg, table, group, cache_ok, *xs, *params, emb_w)
-    return TowersFn.apply(cfg, table, group, cache_ok, *xs, *params)
+        return TowersFn.apply(cfg, table, group, emb_group, cache_ok, *xs, *params, emb_w)
+    return TowersFn.apply(cfg, table, group, None, cache_ok, *xs, *params)

@@ -12,7 +12,9 @@ reference does (enhanced: bare state_dict, train_enhanced.py:75; margin: {'epoch
 Defaults are the reference's (E=300, hidden 512, batch 128, 10 epochs, Adam default
 lr / 1e-3, InfoNCE temperature 0.07 / 0.1). With N ranks each step consumes N*batch
 pairs (weak scaling); negatives are the global batch (losses all-gather the doc
-vectors) and gradients are all-reduced (dist.allreduce_grads).
+vectors) and gradients are all-reduced (dist.allreduce_grads). --train_embeddings fine-tunes
+the Word2Vec table as well (EmbeddingTable + SparseAdam, on any number of ranks) and saves it
+as best_table.pt beside best_model.pt.
 """
 import argparse
 import json
@@ -25,10 +27,11 @@ import torch
 import torch.distributed as tdist
 
 from . import dist as tdp
+from .embedding import EmbeddingTable
 from .losses import HardNegativeMarginLoss, InfoNCELoss
 from .margin import TwoTowerModel
 from .model import EnhancedTwoTowerModel
-from .optim import Adam
+from .optim import Adam, SparseAdam
 from .pretok import PairIds, load_vocab
 
 
@@ -48,6 +51,10 @@ def parse(argv=None):
     ap.add_argument("--max_steps", type=int, default=0, help="stop after this many steps (0: full epochs)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log_every", type=int, default=20)
+    ap.add_argument("--train_embeddings", action="store_true",
+                    help="fine-tune the Word2Vec table (the reference's freeze_embeddings=False): sparse row "
+                         "gradients, SparseAdam, summed across ranks")
+    ap.add_argument("--embed_lr", type=float, default=None, help="SparseAdam lr of the table (default: --lr)")
     ap.add_argument("--mask_duplicates", action="store_true",
                     help="mask in-batch false negatives by the store's group ids (pretok --groups)")
     return ap.parse_args(argv)
@@ -81,7 +88,15 @@ def main(argv=None):
         lr = 1e-3 if a.lr is None else a.lr
         tau = 0.1 if a.temperature is None else a.temperature
     model = model.to(dev).set_compute_dtype(dt).set_process_group(group, overlap_grad_allreduce=world > 1)
-    model.set_embedding_table(vocab.device_table(dev))
+    table = opt_e = None
+    if a.train_embeddings:
+        # every rank starts from the same vectors (set_process_group broadcasts rank 0's) and
+        # takes the same row updates, so the tables stay identical without further traffic
+        table = EmbeddingTable(vocab, trainable=True).to(dev).set_process_group(group)
+        model.set_embedding_table(table)
+        opt_e = SparseAdam(table.parameters(), lr=lr if a.embed_lr is None else a.embed_lr)
+    else:
+        model.set_embedding_table(vocab.device_table(dev))
     if a.loss == "infonce":
         crit = InfoNCELoss(temperature=tau, compute_dtype=dt, process_group=group)
     else:
@@ -89,7 +104,7 @@ def main(argv=None):
         crit = HardNegativeMarginLoss(k=5, margin=0.2, compute_dtype=dt, process_group=group,
                                       max_group_size=data.max_group_size if a.mask_duplicates else None)
     opt = Adam(model.parameters(), lr=lr)
-    params = list(model.parameters())
+    params = list(model.parameters()) + (list(table.parameters()) if table is not None else [])
 
     out = None
     if rank == 0:
@@ -109,10 +124,14 @@ def main(argv=None):
         for i, (q, d, *gids) in enumerate(data.batches(a.batch_size, dev, shuffle=True, seed=a.seed + epoch, rank=rank,
                                                        world=world, with_groups=a.mask_duplicates)):
             opt.zero_grad(set_to_none=True)
+            if opt_e is not None:
+                opt_e.zero_grad(set_to_none=True)
             qv, dv = model(q, d)
             loss = crit(qv, dv, groups=gids[0]) if a.mask_duplicates else crit(qv, dv)
             loss.backward()
-            tdp.allreduce_grads(params, group)
+            tdp.allreduce_grads(params, group)  # the table's rows were summed in the backward: skipped here
+            if opt_e is not None:
+                opt_e.step()  # before Adam, which clears the step guard both honour (optim.SparseAdam)
             opt.step()
             total += loss.detach()  # no host sync per step
             nb += 1
@@ -134,6 +153,8 @@ def main(argv=None):
                 else:
                     torch.save({"epoch": epoch, "model_state_dict": model.state_dict(),
                                 "optimizer_state_dict": opt.state_dict(), "loss": avg}, path)
+                if table is not None:
+                    torch.save(table.state_dict(), os.path.join(out, "best_table.pt"))
         if a.max_steps and steps >= a.max_steps:
             break
     if rank == 0:
